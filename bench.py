@@ -1,8 +1,13 @@
 """Benchmark: federated MaPLe client step (ViT-B/16 + text transformer, deep coupled V-L prompts,
 fwd + bwd + clip_grad_norm_ + SGD) on N MI355X, one client per GPU, FedAvg over RCCL at round end.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run builds the engine, warms up, times the round and prints the headline figure; --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (seeded inputs: the same from run to run).
+--full adds every side measurement (other modes and configs, FedAvg alone, eval rates, rooflines, the round
+wall-time, the CPU baseline), each from runs of its own; the --no-* options choose among those.
 
 One timed "round" = K local steps on every client (one hipGraph replay each, inputs resident in HBM)
 followed by one FedAvg (validity scan + pack + all-reduce + fp16 unpack).  value = images all
@@ -168,6 +173,32 @@ def side_config(name, dev, world, rank, steps=5, warmup=2, seed=0, eot_truncate=
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_GRAD_SAMPLE = 500_000  # gradient elements kept per flat buffer (fixed seeded indices)
+
+
+def dump_outputs(out_dir, eng, loss):
+    """What a caller of the timed path holds after its last step, as float32 / float64 .npy files under out_dir:
+    loss (the step's training loss), logits [B, K], weights_fp16 / weights_fp32 (every trainable weight after the
+    step and the round's FedAvg: the engine's two flat buffers, whole) and grads_fp16 / grads_fp32 (the step's
+    gradients at DUMP_GRAD_SAMPLE fixed, seeded positions of each flat gradient buffer)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(0)
+    arrays = {"loss": np.array([loss], dtype=np.float64),
+              "logits": eng.logits.float().cpu().numpy(),
+              "weights_fp16": eng.flat16.float().cpu().numpy(),
+              "weights_fp32": eng.flat32.cpu().numpy()}
+    for name, g in (("grads_fp16", eng.gflat16), ("grads_fp32", eng.gflat32)):
+        idx = np.sort(rng.choice(g.numel(), size=min(g.numel(), DUMP_GRAD_SAMPLE), replace=False))
+        arrays[name] = g[torch.from_numpy(idx).to(g.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    log(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 # PatternNet's test split: 30 % of its 38 x 800 images (datasets/patternnet.py:33, 66-72 of the reference: 50 % train,
 # 20 % val, the rest test, unshuffled), which the reference's client evaluates after every local epoch
 PATTERNNET_TEST_IMAGES = 38 * 800 - int(0.5 * 38 * 800) - int(0.2 * 38 * 800)
@@ -236,6 +267,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (modes, FedAvg, eval, rooflines, round wall-time, C5, CPU "
+                         "baseline); --cpu-budget, --roofline-kernel and the --no-* options choose among them and "
+                         "do nothing without it")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU-baseline sampling")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-kernel", default="gemm", choices=["gemm", "attention_fwd"])
@@ -249,6 +286,8 @@ def main():
     ap.add_argument("--fused-qkv-attn", default="side", choices=["side", "none", "both", "vision", "text"])
     ap.add_argument("--text-first", action="store_true", help="enqueue the text tower first after each fork")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -322,6 +361,49 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = eng.loss()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)
+
+    step_flop = B * FLOP_PER_IMAGE + K * FLOP_PER_CLASS
+    out = {
+        "metric": "images/sec/node (ViT-B/16 MaPLe fwd+bwd)",
+        "value": world * B * args.steps / elapsed,
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp16",
+        "data": "synthetic (portable counter-based PRNG images/labels/token ids; random-init CLIP ViT-B/16 weights)",
+        "config": {"workload": f"{args.config}: {desc}", "clients": world, "batch_per_client": B,
+                   "global_batch": world * B, "classes": K, "prompt_depth": J, "n_ctx": 2,
+                   "parallelism": f"one federated client per GPU x{world}, FedAvg all-reduce per round",
+                   "round": f"{args.steps} local steps + 1 FedAvg", "hipgraph": not args.no_graph},
+        "fedavg_mode": fed.mode,
+        "fedavg_bucket_mb": 4.0 * (eng.n16 + eng.n32 + 1) / 1e6,
+        "model_tflops": world * step_flop * args.steps / elapsed / 1e12,
+        "model_mfma_frac": world * step_flop * args.steps / elapsed / MFMA_PEAK_F16 / world,
+        "loss": loss,
+    }
+    if args.full:
+        out.update(full_report(args, world, rank, dev, seed, names, eng, fed, batches, load))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_report(args, world, rank, dev, seed, names, eng, fed, batches, load):
+    """Everything `--full` reports beside the headline figure, each from runs of its own after the timed steps:
+    the EOT-truncated and caption modes, FedAvg alone / overlapped / all-reduce, eval rates, the input transform,
+    the per-kernel rooflines, the FedAvg round wall-time, the C5 side config and the CPU baseline (each with its
+    --no-* switch).  Returns the fields to add to the result line."""
+    J, K, B, desc = CONFIGS[args.config]
 
     # ---------------- optional mode, reported separately (SURVEY.md §8(d)): the text tower on the first
     # max(EOT)+1 tokens (bit-identical logits; engine.EngineConfig.eot_truncate).  Same protocol: K graph
@@ -612,8 +694,6 @@ def main():
         except (OSError, ValueError, KeyError):
             traffic = traffic_alg = None
 
-    step_flop = B * FLOP_PER_IMAGE + K * FLOP_PER_CLASS
-    value = world * B * args.steps / elapsed
     if args.roofline_kernel == "gemm":
         roof = {"bound": "mfma", "achieved": ps["tflops"], "peak": MFMA_PEAK_F16 / 1e12, "unit": "TFLOP/s",
                 "frac": ps["tflops"] * 1e12 / MFMA_PEAK_F16, "traffic": traffic, "traffic_unit": "bytes/launch",
@@ -664,29 +744,11 @@ def main():
             c5["eot_truncated_mode"] = side_config("c5", dev, world, rank, eot_truncate=True, probe_gemm=False)
 
     out = {
-        "metric": "images/sec/node (ViT-B/16 MaPLe fwd+bwd)",
-        "value": value,
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp16",
-        "data": "synthetic (portable counter-based PRNG images/labels/token ids; random-init CLIP ViT-B/16 weights)",
-        "config": {"workload": f"{args.config}: {desc}", "clients": world, "batch_per_client": B,
-                   "global_batch": world * B, "classes": K, "prompt_depth": J, "n_ctx": 2,
-                   "parallelism": f"one federated client per GPU x{world}, FedAvg all-reduce per round",
-                   "round": f"{args.steps} local steps + 1 FedAvg", "hipgraph": not args.no_graph},
         "fedavg_ms": fedavg_ms,
-        "fedavg_mode": fed.mode,
         "fedavg_exposed_ms": fedavg_exposed_ms,
         "fedavg_exposed_note": ("world 1: no collective (validity scan + pack + unpack only), nothing to hide"
                                 if world == 1 else f"{fed.mode} exchange over {world} ranks beside the last test()"),
         "fedavg_allreduce_ms": fedavg_allreduce_ms,
-        "fedavg_bucket_mb": 4.0 * (eng.n16 + eng.n32 + 1) / 1e6,
         "fedavg_valid_clients": fed.n_valid(),
         "fedavg_round_wall": fed_round,
         "eot_truncated_mode": eot_mode,
@@ -698,9 +760,6 @@ def main():
                                       "test_engine_group4_per_pass: the forward-only engine test() runs, 400 "
                                       "images (EVAL_GROUP 4 x TEST.BATCH_SIZE 100) per launch, text cached"},
         "input_transform": input_transform,
-        "model_tflops": world * step_flop * args.steps / elapsed / 1e12,
-        "model_mfma_frac": world * step_flop * args.steps / elapsed / MFMA_PEAK_F16 / world,
-        "loss": loss,
         "roofline": roof,
         "attention_roofline": attn_roof,
         "hbm_kernels": hbm_roof,
@@ -709,11 +768,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         log(f"[bench] timing the CPU baseline (oracle, {torch.get_num_threads()} threads) ...")
         out["cpu_baseline"] = cpu_baseline(J, K, B, args.cpu_budget)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -7,8 +7,8 @@
 # steps (knobs are environment variables):
 #   tests      pytest -m gpu, parity reports under gpurun_out/parity   (PYTEST_ARGS, TEST_TIMEOUT)
 #   sel        pytest on the files / node ids in SEL                    (PYTEST_ARGS)
-#   bench      the default bench line, CPU baseline included            (BENCH_ARGS, BENCH_STEPS)
-#   quick      a bench line without the CPU baseline, round wall-time, caption and EOT side runs (BENCH_ARGS)
+#   bench      the bench line with every side measurement (--full), CPU baseline included (BENCH_ARGS, BENCH_STEPS)
+#   quick      a --full bench line without the CPU baseline, round wall-time, caption and EOT side runs (BENCH_ARGS)
 #   prof       rocprofv3 --kernel-trace --stats of a 5-step c4 bench -> gpurun_out/prof  (BENCH_ARGS)
 #   profc5     the same for the C5 side config (bench.py --config c5)
 #   pmc_gemm   FETCH_SIZE / WRITE_SIZE passes over tests/diagnostics/gemm_traffic.py -> gpurun_out/gemm_traffic.json
@@ -27,7 +27,7 @@ set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-QUICK="--no-cpu-baseline --no-round --no-eot-mode --no-c5 --no-caption-mode --no-eval"
+QUICK="--full --no-cpu-baseline --no-round --no-eot-mode --no-c5 --no-caption-mode --no-eval"
 
 step() {
   case "$1" in
@@ -42,7 +42,7 @@ step() {
       rc=$?; echo "sel rc=$rc"; grep -E "^(FAILED|ERROR)|passed|failed" gpurun_out/pytest_sel.log | tail -12
       return $rc ;;
     bench)
-      timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --steps ${BENCH_STEPS:-20} --warmup 5 ${BENCH_ARGS:-} \
+      timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --full --steps ${BENCH_STEPS:-20} --warmup 5 ${BENCH_ARGS:-} \
         > gpurun_out/bench.json 2> gpurun_out/bench.err
       rc=$?; echo "bench rc=$rc"; cut -c1-700 gpurun_out/bench.json; tail -3 gpurun_out/bench.err
       return $rc ;;

@@ -4,7 +4,7 @@ set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
 for pass in fetch:FETCH_SIZE write:WRITE_SIZE mfma:SQ_VALU_MFMA_BUSY_CYCLES,GRBM_GUI_ACTIVE; do
   name=${pass%%:*}; ctr=${pass#*:}
   timeout -k 10 900 rocprofv3 --pmc ${ctr//,/ } --kernel-trace -f csv -d gpurun_out/pmc_$name -o run -- $B > gpurun_out/pmc_$name.log 2>&1
