@@ -127,6 +127,11 @@ def _decode(v: Any) -> Any:
         return v
 
 
+# keys that hold a name or a sequence of numbers ("samples" / (3, 1, 2)): yacs would refuse the second form against
+# a string default, in a YAML file and on the command line (where "3,1,2" already parses as a tuple)
+_NAME_OR_SEQUENCE_KEYS = {"FED.CLIENT_WEIGHTS"}
+
+
 def _check_type(new: Any, old: Any, key: str) -> Any:
     """yacs' _check_and_coerce_cfg_value_type (tuple<->list, int->float and None are allowed)."""
     if old is None or new is None or type(new) is type(old):
@@ -139,6 +144,8 @@ def _check_type(new: Any, old: Any, key: str) -> Any:
         return float(new)
     if isinstance(old, str) and isinstance(new, str):
         return new
+    if key in _NAME_OR_SEQUENCE_KEYS and isinstance(new, (str, list, tuple)):
+        return new if isinstance(new, str) else tuple(new)
     raise ValueError(f"Type mismatch ({type(old)} vs. {type(new)}) with values ({old} vs. {new}) for config key: {key}")
 
 
@@ -203,6 +210,12 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # MI355X additions (federated.py): the bucket exchange -- "ordered" (all_gather +
                            # client-order sum, bit-identical to safe_average_weights) or "allreduce"
                            AGGREGATION="ordered",
+                           # FedAvg weights (McMahan et al.): "uniform" (the reference's plain mean), "samples"
+                           # (each client's training-set size) or one weight per client, e.g. (3, 1, 2)
+                           CLIENT_WEIGHTS="uniform",
+                           # FedProx (Li et al.): mu * (w - w_global) added to every local step's clipped
+                           # gradient; 0 = off (the plain SGD step)
+                           PROX_MU=0.0,
                            # size of each client's synthetic test split (no DATASET.ROOT); 0: one test batch
                            SYNTHETIC_TEST_IMAGES=0,
                            # > 0: the synthetic splits repeat that many generated images (bench timing runs)

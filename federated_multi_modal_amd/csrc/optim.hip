@@ -218,6 +218,91 @@ __global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f
     sgd8_body<float>(p32, g32, b32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x, coef_ptr, hyper);
 }
 
+// FedProx (Li et al., "Federated Optimization in Heterogeneous Networks", MLSys 2020): the local objective gains
+// (mu/2) * ||w - w_global||^2, whose gradient mu * (w - w_global) joins the clipped gradient in the optimizer, as
+// weight decay does.  hyper = {lr, momentum, weight_decay, first_step, halt, mu}.  Every line rounded to T, as
+// torch ops on T tensors round: gc = T(g*coef) (stored back: the stored gradient stays the clipped model
+// gradient); d = T(p - pglob); gp = T(gc + mu*d); d_p = T(gp + wd*p); momentum and parameter update as sgd_kernel.
+// pglob is read only and must not overlap p, g or buf.
+template <typename T>
+MF_DEV void sgd_prox_elem(float pe, float ge, float be, float qe, float coef, float lr, float momentum, float wd,
+                          float mu, bool first, float& p_out, float& g_out, float& b_out) {
+  const float gc = (float)(T)mul32(ge, coef);
+  g_out = gc;
+  const float d = (float)(T)(pe - qe);
+  const float gp = (float)(T)(gc + mul32(mu, d));
+  const float dp = (float)(T)(gp + wd * pe);
+  float b;
+  if (first)
+    b = dp;
+  else
+    b = (float)(T)((float)(T)mul32(be, momentum) + dp);
+  b_out = b;
+  p_out = (float)(T)(pe + (-lr) * b);
+}
+
+template <typename T>
+__global__ void sgd_prox_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf,
+                                const T* __restrict__ pglob, int64_t n, const float* __restrict__ coef_ptr,
+                                const float* __restrict__ hyper) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || hyper[4] != 0.f) return;
+  const bool first = hyper[3] != 0.f;
+  float po, go, bo;
+  sgd_prox_elem<T>((float)p[i], (float)g[i], first ? 0.f : (float)buf[i], (float)pglob[i], coef_ptr[1], hyper[0],
+                   hyper[1], hyper[2], hyper[5], first, po, go, bo);
+  g[i] = (T)go;
+  buf[i] = (T)bo;
+  p[i] = (T)po;
+}
+
+// sgd_prox_kernel on 8 consecutive elements per thread: sgd8_body's accesses plus one 16-byte (fp16) / 2 x 16-byte
+// (fp32) read of the global copy; n % 8 == 0 and 32-byte aligned buffers
+template <typename T>
+MF_DEV void sgd8_prox_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
+                           int64_t n8, int64_t i, const float* __restrict__ coef_ptr,
+                           const float* __restrict__ hyper) {
+  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, float __attribute__((ext_vector_type(8)))>::type;
+  if (i >= n8 || hyper[4] != 0.f) return;
+  const float coef = coef_ptr[1];
+  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], mu = hyper[5];
+  const bool first = hyper[3] != 0.f;
+  V pv = ((V*)p)[i], gv = ((V*)g)[i], bv = first ? V{} : ((V*)buf)[i];
+  const V qv = ((const V*)pglob)[i];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float po, go, bo;
+    sgd_prox_elem<T>((float)pv[e], (float)gv[e], (float)bv[e], (float)qv[e], coef, lr, momentum, wd, mu, first, po,
+                     go, bo);
+    gv[e] = (T)go;
+    bv[e] = (T)bo;
+    pv[e] = (T)po;
+  }
+  ((V*)g)[i] = gv;
+  ((V*)buf)[i] = bv;
+  ((V*)p)[i] = pv;
+}
+
+template <typename T>
+__global__ void sgd8_prox_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf,
+                                 const T* __restrict__ pglob, int64_t n8, const float* __restrict__ coef_ptr,
+                                 const float* __restrict__ hyper) {
+  sgd8_prox_body<T>(p, g, buf, pglob, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+}
+
+// both flat buffers' proximal SGD in one launch, split as sgd8_both_kernel splits them
+__global__ void sgd8_prox_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f16* __restrict__ b16,
+                                      const f16* __restrict__ q16, int64_t n16_8, float* __restrict__ p32,
+                                      float* __restrict__ g32, float* __restrict__ b32, const float* __restrict__ q32,
+                                      int64_t n32_8, unsigned nb16, const float* __restrict__ coef_ptr,
+                                      const float* __restrict__ hyper) {
+  if (blockIdx.x < nb16)
+    sgd8_prox_body<f16>(p16, g16, b16, q16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+  else
+    sgd8_prox_body<float>(p32, g32, b32, q32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x,
+                          coef_ptr, hyper);
+}
+
 // bucket[0:n16] = float(p16), bucket[n16:n16+n32] = p32
 __global__ void pack_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32, int64_t n32,
                             const int* __restrict__ invalid, float* __restrict__ bucket) {
@@ -253,6 +338,52 @@ __global__ void unpack_kernel(const float* __restrict__ bucket, f16* __restrict_
       if (g32) p32[j] = g32[j];
     } else {
       const float v = r16(bucket[i] / n_valid);
+      p32[j] = v;
+      if (g32) g32[j] = v;
+    }
+  }
+}
+
+// FedAvg as McMahan et al. define it ("Communication-Efficient Learning of Deep Networks from Decentralized Data",
+// AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The client's weight travels in its bucket:
+// bucket[0:n] = w * float(p) (the fp32 product is formed and stored here; the sum is formed by
+// reduce_ordered_kernel, so no fused multiply-add spans the two), bucket[n] = w, bucket[n+1] = 1 (its vote);
+// an invalid client writes zeros everywhere.
+__global__ void pack_weighted_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32,
+                                     int64_t n32, const int* __restrict__ invalid, float w,
+                                     float* __restrict__ bucket) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool bad = invalid && invalid[0] != 0;
+  if (i < n16)
+    bucket[i] = bad ? 0.f : w * (float)p16[i];
+  else if (i < n16 + n32)
+    bucket[i] = bad ? 0.f : w * p32[i - n16];
+  else if (i == n16 + n32)
+    bucket[i] = bad ? 0.f : w;
+  else if (i == n16 + n32 + 1)
+    bucket[i] = bad ? 0.f : 1.f;
+}
+// unpack_kernel with the weighted layout: value = fp16(sum / sum of weights), the vote count at bucket[n+1];
+// no votes -> the previous global weights, as unpack_kernel
+__global__ void unpack_weighted_kernel(const float* __restrict__ bucket, f16* __restrict__ p16, int64_t n16,
+                                       float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
+                                       float* __restrict__ g32) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float wsum = bucket[n16 + n32], n_valid = bucket[n16 + n32 + 1];
+  if (i < n16) {
+    if (n_valid == 0.f) {
+      if (g16) p16[i] = g16[i];
+    } else {
+      const f16 v = (f16)(bucket[i] / wsum);
+      p16[i] = v;
+      if (g16) g16[i] = v;
+    }
+  } else if (i < n16 + n32) {
+    const int64_t j = i - n16;
+    if (n_valid == 0.f) {
+      if (g32) p32[j] = g32[j];
+    } else {
+      const float v = r16(bucket[i] / wsum);
       p32[j] = v;
       if (g32) g32[j] = v;
     }
@@ -358,6 +489,78 @@ extern "C" int mf_sgd_step(void* p, void* g, void* buf, int64_t n, int is16, con
     sgd_kernel<f16><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, n, coef, hyper);
   else
     sgd_kernel<float><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, n, coef, hyper);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// mf_sgd_step with the FedProx term mu * (p - pglob), mu = hyper[5] (a 6-float hyper)
+extern "C" int mf_sgd_prox_step(void* p, void* g, void* buf, const void* pglob, int64_t n, int is16, const float* coef,
+                                const float* hyper, void* stream) {
+  if (n <= 0) return 0;
+  if (!pglob) return mf_set_error("mf_sgd_prox_step: no global copy", -1);
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = n % 8 == 0 && (uintptr_t)p % 32 == 0 && (uintptr_t)g % 32 == 0 && (uintptr_t)buf % 32 == 0 &&
+                   (uintptr_t)pglob % 32 == 0;
+  if (vec && is16)
+    sgd8_prox_kernel<f16><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n / 8, coef,
+                                                       hyper);
+  else if (vec)
+    sgd8_prox_kernel<float><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob,
+                                                         n / 8, coef, hyper);
+  else if (is16)
+    sgd_prox_kernel<f16><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n, coef, hyper);
+  else
+    sgd_prox_kernel<float><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, n, coef,
+                                                    hyper);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// mf_optimizer_step with the proximal SGD launch: the partial sums and the coefficient launch are the same kernels
+// (the clip norm is the model gradient's, without the proximal term)
+extern "C" int mf_optimizer_step_prox(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
+                                      int64_t n32, const void* chunks, int nchunks, float max_norm, float* part,
+                                      float* out, float* hyper, const float* halt_src, const int* input_flag,
+                                      const void* glob16, const float* glob32, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if ((n16 > 0 && !glob16) || (n32 > 0 && !glob32)) return mf_set_error("mf_optimizer_step_prox: no global copy", -1);
+  if (nchunks > 0) {
+    sumsq_chunks_kernel<<<nchunks, 256, 0, st>>>((const f16*)g16, g32, (const Chunk*)chunks, part);
+    MF_CHECK_LAUNCH();
+  }
+  clip_coef_kernel<<<1, 1024, 0, st>>>(part, (const Chunk*)chunks, nchunks, max_norm, out, hyper, halt_src,
+                                       input_flag);
+  MF_CHECK_LAUNCH();
+  const bool vec16 = n16 % 8 == 0 && (uintptr_t)p16 % 32 == 0 && (uintptr_t)g16 % 32 == 0 &&
+                     (uintptr_t)b16 % 32 == 0 && (uintptr_t)glob16 % 32 == 0;
+  const bool vec32 = n32 % 8 == 0 && (uintptr_t)p32 % 32 == 0 && (uintptr_t)g32 % 32 == 0 &&
+                     (uintptr_t)b32 % 32 == 0 && (uintptr_t)glob32 % 32 == 0;
+  if (vec16 && vec32 && n16 + n32 > 0) {
+    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
+    sgd8_prox_both_kernel<<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, (const f16*)glob16, n16 / 8,
+                                                       p32, g32, b32, glob32, n32 / 8, nb16, out, hyper);
+    MF_CHECK_LAUNCH();
+    return 0;
+  }
+  int rc = mf_sgd_prox_step(p16, g16, b16, glob16, n16, 1, out, hyper, stream);
+  return rc ? rc : mf_sgd_prox_step(p32, g32, b32, glob32, n32, 0, out, hyper, stream);
+}
+
+extern "C" int mf_fedavg_pack_weighted(const void* p16, int64_t n16, const float* p32, int64_t n32,
+                                       const int* invalid_flag, float weight, float* bucket, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack_weighted: negative size", -1);
+  if (!(weight > 0.f) || __builtin_isinf(weight)) return mf_set_error("mf_fedavg_pack_weighted: weight not in (0, inf)", -1);
+  pack_weighted_kernel<<<nblk(n16 + n32 + 2), 256, 0, (hipStream_t)stream>>>((const f16*)p16, n16, p32, n32,
+                                                                             invalid_flag, weight, bucket);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mf_fedavg_unpack_weighted(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32,
+                                         void* g16, float* g32, void* stream) {
+  if (n16 + n32 <= 0) return 0;
+  unpack_weighted_kernel<<<nblk(n16 + n32), 256, 0, (hipStream_t)stream>>>(bucket, (f16*)p16, n16, p32, n32, (f16*)g16,
+                                                                           g32);
   MF_CHECK_LAUNCH();
   return 0;
 }

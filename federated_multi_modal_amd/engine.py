@@ -534,15 +534,19 @@ class MapleEngine:
             self._token_table = None if tok is None else torch.as_tensor(np.asarray(tok, dtype=np.float32))
             self._table_owner = self
             self._build_text_constants()
-            # {lr, momentum, weight_decay, first_step, halt}: read by the SGD kernels from device memory
-            self.hyper = torch.tensor([0.0, cfg.momentum, cfg.weight_decay, 1.0, 0.0], device=self.device, dtype=F32)
+            # {lr, momentum, weight_decay, first_step, halt, mu}: read by the SGD kernels from device memory (mu: the
+            # FedProx coefficient, read by the proximal step only -- set_proximal)
+            self.hyper = torch.tensor([0.0, cfg.momentum, cfg.weight_decay, 1.0, 0.0, 0.0], device=self.device,
+                                      dtype=F32)
+            # set_proximal's state, one dict shared with every engine built on these parameters (shared=)
+            self._prox = {"glob": None, "captured": False}
         else:
             assert shared.K == self.K and shared.J == self.J and shared.device == self.device
             assert shared.cfg.eot_truncate == cfg.eot_truncate
             for a in ("n16", "n32", "flat16", "flat32", "gflat16", "gflat32", "mom16", "mom32", "P", "G",
                       "trainable_names", "conv_w", "chunks", "nchunks", "norm_part", "clip_out", "WT", "tokenized",
                       "token_prefix", "token_suffix", "token_suffix_run", "text_len", "eot_rows", "hyper",
-                      "clip_logit_scale", "_table_owner"):
+                      "clip_logit_scale", "_table_owner", "_prox"):
                 setattr(self, a, getattr(shared, a))
         G2 = d.grid * d.grid
         self.Lv = G2 + 1 + cfg.n_ctx
@@ -992,6 +996,30 @@ class MapleEngine:
     def set_lr(self, lr: float):
         self.hyper[0] = lr
 
+    def set_proximal(self, mu: float, glob16: torch.Tensor, glob32: torch.Tensor):
+        """FedProx (Li et al., MLSys 2020): every local step adds mu * (w - w_global) to the clipped gradient
+        (mf_optimizer_step_prox).  glob16 / glob32: device buffers holding the last global weights in the layout of
+        flat16 / flat32 (FedAvgBucket.global16 / global32, refreshed in place by every unpack); their pointers go
+        into the captured step, so they must stay alive and in place, and this must run before any capture."""
+        if self._prox["captured"]:
+            raise RuntimeError("set_proximal after a training step was captured: the captured graph holds the "
+                               "plain SGD launch; call it before the first capture_train_step()")
+        for name, t, ref in (("glob16", glob16, self.flat16), ("glob32", glob32, self.flat32)):
+            if (t.dtype != ref.dtype or t.device != ref.device or t.numel() != ref.numel() or not t.is_contiguous()
+                    or (t.numel() and t.data_ptr() == ref.data_ptr())):
+                raise ValueError(f"{name}: a contiguous {ref.dtype} buffer of {ref.numel()} elements on {ref.device}, "
+                                 "other than the trainables themselves, is required")
+        self._prox["glob"] = (glob16, glob32)
+        self.set_prox_mu(mu)
+
+    def set_prox_mu(self, mu: float):
+        """The proximal coefficient, read from device memory by the (captured) step: change it between rounds
+        without a recapture.  Has an effect only after set_proximal."""
+        mu = float(mu)
+        if not math.isfinite(mu) or mu < 0.0:
+            raise ValueError(f"FedProx mu must be finite and >= 0, got {mu}")
+        self.hyper[5] = mu
+
     def reset_momentum(self):
         """broadcast_weights deletes the SGD state (trainers/maple_fed.py:331-335)."""
         self.hyper[3] = 1.0
@@ -1004,9 +1032,15 @@ class MapleEngine:
         later one of the epoch updates the weights; the SGD kernels skip while halt is set.  The trainer
         clears it at the start of an epoch and reports the failure (MaPLe.run_epoch)."""
         # the halt latch, clip coefficient and both flat buffers' SGD in three launches (mf_optimizer_step)
-        ops.optimizer_step(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32, self.chunks,
-                           self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out, self.hyper,
-                           self.loss_out[3:4], self.input_flag)
+        glob = self._prox["glob"]
+        if glob is None:
+            ops.optimizer_step(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32,
+                               self.chunks, self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out,
+                               self.hyper, self.loss_out[3:4], self.input_flag)
+        else:  # FedProx: the same three launches, the SGD one reading the global copy too (set_proximal)
+            ops.optimizer_step_prox(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32,
+                                    self.chunks, self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out,
+                                    self.hyper, self.loss_out[3:4], self.input_flag, glob[0], glob[1])
         # the momentum buffers now exist (first_step -> 0) unless the update was skipped
         self.hyper[3:4].mul_(self.hyper[4:5])  # device ops, legal inside graph capture
 
@@ -1032,6 +1066,7 @@ class MapleEngine:
             self.forward_backward()
             self.optimizer_step()
         self.hyper[3] = first  # capture does not execute the step
+        self._prox["captured"] = True
         return g
 
     # ------------------------------------------------------------------ state

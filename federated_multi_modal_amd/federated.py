@@ -40,9 +40,16 @@ on such late failures with one 4-byte all_reduce and, when there is one, re-pack
 Frozen tensors are bit-identical across clients, so leaving them out of the bucket is result-preserving
 (an fp32 mean of identical fp16 values is exact).  With world_size 1 (or no process
 group) the same kernels run with no collective.
+
+Sample-weighted FedAvg (McMahan et al., AISTATS 2017; FED.CLIENT_WEIGHTS, off by default): a bucket built with
+weight=w packs [w * trainables | w | vote] (mf_fedavg_pack_weighted), the exchange sums the n + 2 floats exactly as
+it sums the n + 1 of the plain layout, and unpack divides by the summed weights (mf_fedavg_unpack_weighted).  The
+fp32 products are rounded in the pack kernel and summed in client order, so the "ordered" result equals the torch
+expression acc = w0*x0; acc += wc*xc ...; (acc / sum w).half() bit for bit at any world size.
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Optional, Sequence
 
 import torch
@@ -62,7 +69,48 @@ class _HipKernels:
     nonfinite_flag = staticmethod(ops.nonfinite_flag)
     fedavg_pack = staticmethod(ops.fedavg_pack)
     fedavg_unpack = staticmethod(ops.fedavg_unpack)
+    fedavg_pack_weighted = staticmethod(ops.fedavg_pack_weighted)
+    fedavg_unpack_weighted = staticmethod(ops.fedavg_unpack_weighted)
     fedavg_reduce_ordered = staticmethod(ops.fedavg_reduce_ordered)
+
+
+def resolve_client_weights(spec, sample_counts: Sequence[int], num_clients: int) -> Optional[List[float]]:
+    """FED.CLIENT_WEIGHTS -> one FedAvg weight per client, or None for the unweighted mean.
+
+    "uniform" -> None; "samples" -> sample_counts (each client's number of training samples) as floats; a list,
+    a tuple or a comma-separated string -> those values.  ValueError for a wrong length, a weight that is
+    non-finite or <= 0, or a sample count >= 2**24 (not exact in fp32, the bucket's number format)."""
+    if isinstance(spec, str):
+        name = spec.strip().lower()
+        if name == "uniform":
+            return None
+        if name == "samples":
+            counts = list(sample_counts)
+            if len(counts) != num_clients:
+                raise ValueError(f"FED.CLIENT_WEIGHTS samples: {len(counts)} sample counts for {num_clients} clients")
+            for c in counts:
+                if int(c) != c or c >= 2 ** 24:
+                    raise ValueError(f"FED.CLIENT_WEIGHTS samples: a count of {c} is not exact in fp32 (>= 2**24) "
+                                     "or not an integer; give explicit weights")
+            vals = [float(c) for c in counts]
+        else:
+            try:
+                vals = [float(v) for v in spec.split(",")]
+            except ValueError:
+                raise ValueError(f'FED.CLIENT_WEIGHTS {spec!r}: "uniform", "samples" or one weight per client') from None
+    elif isinstance(spec, (list, tuple)):
+        try:
+            vals = [float(v) for v in spec]
+        except (TypeError, ValueError):
+            raise ValueError(f"FED.CLIENT_WEIGHTS {spec!r}: the weights must be numbers") from None
+    else:
+        raise ValueError(f'FED.CLIENT_WEIGHTS {spec!r}: "uniform", "samples" or one weight per client')
+    if len(vals) != num_clients:
+        raise ValueError(f"FED.CLIENT_WEIGHTS: {len(vals)} weights for {num_clients} clients")
+    for v in vals:
+        if not math.isfinite(v) or v <= 0.0:
+            raise ValueError(f"FED.CLIENT_WEIGHTS: weight {v} is not finite and > 0")
+    return vals
 
 
 def _world(group) -> int:
@@ -72,16 +120,22 @@ def _world(group) -> int:
 class FedAvgBucket:
     """One client's bucket.  `engine` needs: device, n16, n32, flat16 (fp16 trainables), flat32 (fp32
     trainables) and after_weights_loaded().  `kernels` defaults to the HIP kernels; tests substitute host
-    restatements to exercise the collective protocol on CPU ranks (gloo).
+    restatements to exercise the collective protocol on CPU ranks (gloo).  `weight` (finite, > 0) selects the
+    sample-weighted layout and kernels (module docstring); None is the reference's plain mean.
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
     exchange through one FedAvgExchange over all their buckets."""
 
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None, kernels=_HipKernels,
-                 mode: str = "ordered", shard_single: bool = False):
+                 mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
+        if weight is not None:
+            weight = float(weight)
+            if not math.isfinite(weight) or weight <= 0.0:
+                raise ValueError(f"FedAvg client weight {weight}: finite and > 0")
+        self.weight = weight
         self.e = engine
         self.group = group
         self.k = kernels
@@ -91,12 +145,15 @@ class FedAvgBucket:
         n = engine.n16 + engine.n32
         self.world = _world(group)
         # [bucket | count | zero padding to a multiple of the world size]: one contiguous buffer so the
-        # mean and the valid-client count travel in the same collectives
-        padded = -(-(n + 1) // self.world) * self.world
+        # mean and the valid-client count travel in the same collectives.  With a client weight (every client
+        # of a run has one or none): [weight * bucket | weight | count | padding], so the weighted sum, the sum
+        # of the weights and the count travel together and the exchange itself is unchanged
+        tail = 1 if weight is None else 2
+        padded = -(-(n + tail) // self.world) * self.world
         self.pbuf = torch.zeros(padded, device=dev, dtype=torch.float32)
-        self.buf = self.pbuf[:n + 1]
+        self.buf = self.pbuf[:n + tail]
         self.bucket = self.buf[:n]
-        self.count = self.buf[n:]
+        self.count = self.buf[n + tail - 1:]
         self.flag = torch.zeros(1, device=dev, dtype=torch.int32)
         self.failed = False
         # the last global weights (what broadcast_weights would load): restored when a round fails
@@ -117,13 +174,19 @@ class FedAvgBucket:
             self.flag.zero_()
             self.k.nonfinite_flag(e.flat16, self.flag)
             self.k.nonfinite_flag(e.flat32, self.flag)
-        self.k.fedavg_pack(e.flat16, e.flat32, self.flag, self.buf)
+        if self.weight is None:
+            self.k.fedavg_pack(e.flat16, e.flat32, self.flag, self.buf)
+        else:
+            self.k.fedavg_pack_weighted(e.flat16, e.flat32, self.flag, self.weight, self.buf)
 
     def unpack(self):
         """The fp16-rounded mean into every trainable (device-side n_valid; n_valid == 0 leaves the weights
         at the previous global copy).  No host synchronisation."""
         e = self.e
-        self.k.fedavg_unpack(self.buf, e.flat16, e.flat32, self.global16, self.global32)
+        if self.weight is None:
+            self.k.fedavg_unpack(self.buf, e.flat16, e.flat32, self.global16, self.global32)
+        else:
+            self.k.fedavg_unpack_weighted(self.buf, e.flat16, e.flat32, self.global16, self.global32)
         e.after_weights_loaded()
 
     def snapshot(self):
@@ -180,6 +243,8 @@ class FedAvgExchange:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         self.b = list(buckets)
         assert self.b and len({x.pbuf.numel() for x in self.b}) == 1
+        # one layout per exchange: every bucket weighted (n + 2 floats) or none (n + 1)
+        assert len({x.weight is None for x in self.b}) == 1, "weighted and unweighted buckets in one exchange"
         b0 = self.b[0]
         self.group, self.mode, self.k = group, mode, b0.k
         self.C = len(self.b)

@@ -625,6 +625,86 @@ def optimizer_step(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part
     _rec(ev)
 
 
+def _check_flat(name, t, dtype, numel=None):
+    if t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        want = f"contiguous {dtype}" + (f" of {numel} elements" if numel is not None else "")
+        raise ValueError(f"{name}: {want} required, got {t.dtype} {tuple(t.shape)}"
+                         f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def _check_prox_hyper(hyper):
+    if hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.numel() < 6:
+        raise ValueError("hyper: contiguous fp32 {lr, momentum, weight_decay, first_step, halt, mu} (6 floats) "
+                         f"required, got {hyper.dtype} {tuple(hyper.shape)}")
+
+
+def sgd_prox_step(p, g, buf, pglob, coef, hyper):
+    """sgd_step with the FedProx term mu * (p - pglob) added to the clipped gradient (mf_sgd_prox_step).
+    hyper: device fp32 tensor {lr, momentum, weight_decay, first_step, halt, mu}; pglob: the last global weights,
+    p's dtype and size, a buffer of its own."""
+    if p.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"p: fp16 or fp32 required, got {p.dtype}")
+    _check_flat("p", p, p.dtype)
+    for name, t in (("g", g), ("buf", buf), ("pglob", pglob)):
+        _check_flat(name, t, p.dtype, p.numel())
+    if p.numel() and pglob.data_ptr() == p.data_ptr():
+        raise ValueError("pglob: a buffer of its own required (it is p)")
+    _check_prox_hyper(hyper)
+    # sgd_step's streams plus one read of the global copy
+    ev = _hbm(f"sgd_prox_step/{'f16' if p.dtype == torch.float16 else 'f32'}", p.numel() * 6.0 * p.element_size())
+    call("mf_sgd_prox_step", _p(p), _p(g), _p(buf), _p(pglob), p.numel(), int(p.dtype == torch.float16), _p(coef),
+         _p(hyper), _s())
+    _rec(ev)
+
+
+def optimizer_step_prox(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
+                        input_flag=None, glob16=None, glob32=None):
+    """optimizer_step with the proximal SGD launch (mf_optimizer_step_prox): glob16 / glob32 are the last global
+    weights of the two flat buffers, hyper has 6 floats (mu at [5])."""
+    if glob16 is None or glob32 is None:
+        raise ValueError("optimizer_step_prox: glob16 and glob32 (the global copies) are required")
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    for name, t, ref in (("g16", g16, p16), ("b16", b16, p16), ("glob16", glob16, p16), ("g32", g32, p32),
+                         ("b32", b32, p32), ("glob32", glob32, p32)):
+        _check_flat(name, t, ref.dtype, ref.numel())
+    if (p16.numel() and glob16.data_ptr() == p16.data_ptr()) or (p32.numel() and glob32.data_ptr() == p32.data_ptr()):
+        raise ValueError("glob16 / glob32: buffers of their own required")
+    _check_prox_hyper(hyper)
+    nb = g16.numel() * 2.0 + g32.numel() * 4.0 + p16.numel() * 12.0 + p32.numel() * 24.0
+    ev = _hbm("optimizer_step_prox", nb)  # optimizer_step's bytes plus one read of the global copies
+    call("mf_optimizer_step_prox", _p(p16), _p(g16), _p(b16), p16.numel(), _p(p32), _p(g32), _p(b32), p32.numel(),
+         _p(chunks), nchunks, float(max_norm), _p(part), _p(out), _p(hyper), _p(halt_src), _p(input_flag),
+         _p(glob16), _p(glob32), _s())
+    _rec(ev)
+
+
+def fedavg_pack_weighted(p16, p32, invalid_flag, weight, bucket):
+    """bucket: n16 + n32 + 2 floats = [weight * trainables | weight | vote] (mf_fedavg_pack_weighted)."""
+    import math
+    weight = float(weight)
+    if not math.isfinite(weight) or weight <= 0.0:
+        raise ValueError(f"weight: finite and > 0 required, got {weight}")
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    _check_flat("bucket", bucket, torch.float32, p16.numel() + p32.numel() + 2)
+    call("mf_fedavg_pack_weighted", _p(p16), p16.numel(), _p(p32), p32.numel(), _p(invalid_flag), weight, _p(bucket),
+         _s())
+
+
+def fedavg_unpack_weighted(bucket, p16, p32, g16=None, g32=None):
+    """fp16(bucket[i] / bucket[n]) into p16 / p32 and g16 / g32; vote count bucket[n+1] == 0 restores from g16 / g32."""
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    if bucket.dtype != torch.float32 or not bucket.is_contiguous() or bucket.numel() < p16.numel() + p32.numel() + 2:
+        raise ValueError("bucket: contiguous fp32 of at least n16 + n32 + 2 floats required")
+    if g16 is not None:
+        _check_flat("g16", g16, torch.float16, p16.numel())
+    if g32 is not None:
+        _check_flat("g32", g32, torch.float32, p32.numel())
+    call("mf_fedavg_unpack_weighted", _p(bucket), _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16), _p(g32), _s())
+
+
 def fedavg_pack(p16, p32, invalid_flag, bucket):
     """bucket: n16 + n32 + 1 floats (last = this client's valid vote)."""
     assert bucket.numel() == p16.numel() + p32.numel() + 1

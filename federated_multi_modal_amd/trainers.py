@@ -33,7 +33,7 @@ import torch.distributed as dist
 from . import ops
 from .data import DATASET_CLASSES, SyntheticClientDataManager, unified_classnames
 from .engine import EngineConfig, MapleEngine
-from .federated import FedAvgBucket, FedAvgExchange, FederatedAbort
+from .federated import FedAvgBucket, FedAvgExchange, FederatedAbort, resolve_client_weights
 from .captions import caption_tokens, draw_caption_weights, has_captions
 from .modules import CustomCLIP
 from .schedule import HostLR
@@ -572,18 +572,54 @@ class MaPLeFederated(TrainerX):
                 seed=max(self.cfg.SEED, 0), unique_images=n_unique)
         self.train_loader_x = self.val_loader = self.test_loader = self.dm = None
 
+    def _client_sample_counts(self, spec) -> List[int]:
+        """Training-set size of every client, in client order, for FED.CLIENT_WEIGHTS "samples" (else not
+        needed: []).  A rank holds its own clients' loaders only, so the ranks gather the full list: each packs
+        with its own clients' weights alone, but every rank validates and logs the same list."""
+        if not (isinstance(spec, str) and spec.strip().lower() == "samples"):
+            return []
+        local = []
+        for i in self._local_client_ids():
+            loader = self.client_data_managers[i].train_loader
+            labels = loader.labels if hasattr(loader, "labels") else loader.s.labels
+            local.append(int(labels.numel()))
+        if not self.distributed:
+            return local
+        gathered = [None] * dist.get_world_size()
+        dist.all_gather_object(gathered, local)
+        return [n for part in gathered for n in part]
+
     def build_model(self):
-        """trainers/maple_fed.py:164-176."""
+        """trainers/maple_fed.py:164-176, plus the two options the reference lacks (both off by default):
+        FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.) and FED.PROX_MU (FedProx, Li et al.)."""
         global_classnames = list(self.lab2cname.values())
+        get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
+        mu = float(get("PROX_MU", 0.0))
+        if mu < 0.0 or mu != mu:
+            raise ValueError(f"FED.PROX_MU {mu}: the FedProx coefficient is >= 0 (0 = off)")
+        spec = get("CLIENT_WEIGHTS", "uniform")
+        self.client_weights = resolve_client_weights(spec, self._client_sample_counts(spec), self.num_clients)
+        if self.client_weights is not None and self.rank == 0:
+            total = sum(self.client_weights)
+            print("[INFO] FedAvg client weights: " + ", ".join(
+                f"client {i}: {w:g} ({100.0 * w / total:.1f} %)" for i, w in enumerate(self.client_weights)))
         self.clients = []
         for i in self._local_client_ids():
             self.clients.append(MaPLe(self.cfg, client_id=i, classnames=global_classnames,
                                       dm=self.client_data_managers[i], device=self.device))
         c0 = self.clients[0]
         self.register_model("MultiModalPromptLearner_Aggregator", c0.model, None, None)
-        mode = self.cfg.FED.get("AGGREGATION", "ordered") if hasattr(self.cfg.FED, "get") else "ordered"
-        self.fed = [FedAvgBucket(c.engine, mode=mode) for c in self.clients]
+        mode = get("AGGREGATION", "ordered")
+        cw = self.client_weights
+        self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id])
+                    for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode)
+        if mu > 0.0:
+            # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
+            # pointers go in before a client captures its training step
+            print(f"[INFO] FedProx: mu = {mu:g}")
+            for c, fed in zip(self.clients, self.fed):
+                c.engine.set_proximal(mu, fed.global16, fed.global32)
         self.global_weights = self.clients[0].model.state_dict()
 
     # ---------------------------------------------------------------- round loop
@@ -711,8 +747,26 @@ class MaPLeFederated(TrainerX):
         return self.fed[0].n_valid()
 
     # ---------------------------------------------------------------- reference utilities
-    def safe_average_weights(self, local_dicts, valid_clients=None):
-        """trainers/maple_fed.py:309-315 on state dicts (host API; the round loop averages on device)."""
+    def safe_average_weights(self, local_dicts, valid_clients=None, weights=None):
+        """trainers/maple_fed.py:309-315 on state dicts (host API; the round loop averages on device).
+        weights (one per dict, finite and > 0): the sample-weighted mean sum_c w_c x_c / sum_c w_c instead, formed
+        as the device path forms it -- fp32 products summed in client order, one division, `.half()`."""
+        if weights is not None:
+            ws = [float(w) for w in weights]
+            if len(ws) != len(local_dicts) or any(not (w > 0.0) or w == float("inf") for w in ws):
+                raise ValueError("safe_average_weights: one finite weight > 0 per state dict")
+            wsum = torch.tensor(ws[0], dtype=torch.float32)
+            for w in ws[1:]:
+                wsum = wsum + torch.tensor(w, dtype=torch.float32)
+            avg = {}
+            for key in local_dicts[0].keys():
+                stacked = torch.stack([sd[key].float() for sd in local_dicts])
+                stacked = torch.nan_to_num(stacked, nan=0.0, posinf=1e4, neginf=-1e4)
+                acc = stacked[0] * ws[0]
+                for w, x in zip(ws[1:], stacked[1:]):
+                    acc = acc + x * w
+                avg[key] = (acc / wsum).half()
+            return avg
         avg = {}
         for key in local_dicts[0].keys():
             stacked = torch.stack([sd[key].float() for sd in local_dicts])

@@ -217,6 +217,35 @@ int mf_sgd_step(void* p, void* g, void* buf, int64_t n, int is16, const float* c
 int mf_optimizer_step(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32, int64_t n32,
                       const void* chunks, int nchunks, float max_norm, float* part, float* out, float* hyper,
                       const float* halt_src, const int* input_flag, void* stream);
+/* FedProx local step (Li, Sahu, Zaheer, Sanjabi, Talwalkar, Smith: "Federated Optimization in Heterogeneous
+ * Networks", MLSys 2020): mf_sgd_step with the proximal gradient mu * (p - pglob) added after clipping, in the
+ * optimizer, as weight decay is.  hyper (device) has 6 floats here: {lr, momentum, weight_decay, first_step, halt,
+ * mu}.  Per element, every line rounded to the buffer's dtype T: g = gc = T(g * coef) (the stored gradient stays
+ * the clipped model gradient); d = T(p - pglob); gp = T(gc + mu * d); d_p = T(gp + wd * p); momentum and parameter
+ * update as mf_sgd_step.  mu == 0 (or pglob == p element-wise) gives mf_sgd_step's result bit for bit.  pglob
+ * (n elements of T, the last global weights) is only read and must not overlap p, g or buf.               */
+int mf_sgd_prox_step(void* p, void* g, void* buf, const void* pglob, int64_t n, int is16, const float* coef,
+                     const float* hyper, void* stream);
+/* mf_optimizer_step with the proximal SGD launch (three launches; the clip norm is the model gradient's): its
+ * arguments plus the global copies of the two flat buffers.  Bit-identical to mf_clip_grad_norm + the halt latch +
+ * mf_sgd_prox_step(fp16) + mf_sgd_prox_step(fp32).                                                           */
+int mf_optimizer_step_prox(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
+                           int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
+                           float* hyper, const float* halt_src, const int* input_flag, const void* glob16,
+                           const float* glob32, void* stream);
+/* Sample-weighted FedAvg (McMahan, Moore, Ramage, Hampson, Aguera y Arcas: "Communication-Efficient Learning of
+ * Deep Networks from Decentralized Data", AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The weight travels
+ * in the bucket, n = n16 + n32: pack writes n + 2 floats, bucket[0:n] = fp32(weight) * float(p) (0 if
+ * *invalid_flag), bucket[n] = weight (0 if invalid), bucket[n+1] = the vote (1 valid / 0 invalid); weight must be
+ * finite and > 0.  After the sum over the clients (mf_fedavg_reduce_ordered or an all-reduce) unpack writes
+ * fp16(bucket[i] / bucket[n]) into every trainable and into g16/g32; a vote count bucket[n+1] == 0 restores the
+ * trainables from g16/g32, as mf_fedavg_unpack does.  The product is rounded to fp32 before the sum (no fused
+ * multiply-add across pack and reduce), so equal power-of-two weights give mf_fedavg_pack/unpack's result bit for
+ * bit.                                                                                                         */
+int mf_fedavg_pack_weighted(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
+                            float weight, float* bucket, void* stream);
+int mf_fedavg_unpack_weighted(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32, void* g16,
+                              float* g32, void* stream);
 /* bucket[0:n16+n32] = this client's trainables as fp32 (0 if *invalid_flag), bucket[n16+n32] = its vote
  * (1 valid / 0 invalid); after an all-reduce(SUM) of the n16+n32+1 floats, unpack writes
  * fp16(sum / n_valid) into every trainable and into the global copy g16/g32, n_valid read from
