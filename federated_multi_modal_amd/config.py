@@ -216,6 +216,11 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # FedProx (Li et al.): mu * (w - w_global) added to every local step's clipped
                            # gradient; 0 = off (the plain SGD step)
                            PROX_MU=0.0,
+                           # FedOpt server optimizer on the round's mean (federated.ServerOptimizer): "none" (the
+                           # reference: the mean becomes the global model), "fedavgm" (Hsu et al.), "fedadagrad",
+                           # "fedadam", "fedyogi" (Reddi et al.); eta, beta1, beta2 and tau of those papers
+                           SERVER_OPT="none", SERVER_LR=1.0, SERVER_MOMENTUM=0.9, SERVER_BETA2=0.99,
+                           SERVER_TAU=1e-3,
                            # size of each client's synthetic test split (no DATASET.ROOT); 0: one test batch
                            SYNTHETIC_TEST_IMAGES=0,
                            # > 0: the synthetic splits repeat that many generated images (bench timing runs)

@@ -390,6 +390,175 @@ __global__ void unpack_weighted_kernel(const float* __restrict__ bucket, f16* __
   }
 }
 
+// FedOpt server optimizers: FedAvgM (Hsu, Qi, Brown: "Measuring the Effects of Non-Identical Data Distribution for
+// Federated Visual Classification", 2019) and FedAdagrad / FedAdam / FedYogi (Reddi et al., "Adaptive Federated
+// Optimization", ICLR 2021, Algorithm 2, no bias correction).  The step replaces unpack_kernel on the summed bucket:
+// the mean is the pseudo-gradient's target, the server keeps an fp32 master copy x of the trainables (a step
+// eta * m / (sqrt(v) + tau) is lost in an fp16 weight) with its moments m and v, and the clients receive fp16(x),
+// what a `.half()` state dict would hold.  Per element, every binary operation rounded to fp32 once, no fused
+// multiply-add (the file's contract(off)):
+//   mean = sum / d;  delta = mean - x
+//   fedavgm:    m = b1*m + delta;                               upd = m
+//   adaptive:   m = b1*m + (1-b1)*delta;  s = delta*delta
+//     fedadagrad: v = v + s
+//     fedadam:    v = b2*v + (1-b2)*s
+//     fedyogi:    v = v - ((1-b2)*s) * sign(v - s)   (sign(0) = 0)
+//                                                               upd = m / (sqrtf(v) + tau)
+//   x = x + eta*upd
+enum { FEDOPT_AVGM = 1, FEDOPT_ADAGRAD = 2, FEDOPT_ADAM = 3, FEDOPT_YOGI = 4 };
+
+struct FedOptHyper {
+  int opt;
+  float b1, b2, tau, eta;
+};
+
+MF_DEV void fedopt_elem(const FedOptHyper& h, float omb1, float omb2, float sum, float d, float& x, float& m,
+                        float& v) {
+  const float mean = sum / d;
+  const float delta = mean - x;
+  float upd;
+  if (h.opt == FEDOPT_AVGM) {
+    m = h.b1 * m + delta;
+    upd = m;
+  } else {
+    m = h.b1 * m + omb1 * delta;
+    const float s = delta * delta;
+    if (h.opt == FEDOPT_ADAGRAD) {
+      v = v + s;
+    } else if (h.opt == FEDOPT_ADAM) {
+      v = h.b2 * v + omb2 * s;
+    } else {
+      const float t = v - s;
+      const float sg = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
+      v = v - (omb2 * s) * sg;
+    }
+    upd = m / (sqrtf(v) + h.tau);
+  }
+  x = x + h.eta * upd;
+}
+
+// one element per thread over [fp16 trainables | fp32 trainables]; d = bucket[n] (the vote count of the plain
+// layout, the summed weights of the weighted one), votes = bucket[n + weighted].  No votes: the client goes back to
+// the global copy and the server state keeps its bits.
+__global__ void fedopt_step_kernel(const float* __restrict__ bucket, int weighted, FedOptHyper h,
+                                   float* __restrict__ x, float* __restrict__ m, float* __restrict__ v,
+                                   f16* __restrict__ p16, int64_t n16, float* __restrict__ p32, int64_t n32,
+                                   f16* __restrict__ g16, float* __restrict__ g32) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n = n16 + n32;
+  if (i >= n) return;
+  const float d = bucket[n], votes = bucket[n + weighted];
+  if (votes == 0.f) {
+    if (i < n16)
+      p16[i] = g16[i];
+    else
+      p32[i - n16] = g32[i - n16];
+    return;
+  }
+  const bool adaptive = h.opt != FEDOPT_AVGM;
+  float xe = x[i], me = m[i], ve = adaptive ? v[i] : 0.f;
+  fedopt_elem(h, 1.f - h.b1, 1.f - h.b2, bucket[i], d, xe, me, ve);
+  x[i] = xe;
+  m[i] = me;
+  if (adaptive) v[i] = ve;
+  const f16 val = (f16)xe;
+  if (i < n16) {
+    p16[i] = val;
+    g16[i] = val;
+  } else {
+    p32[i - n16] = (float)val;
+    g32[i - n16] = (float)val;
+  }
+}
+
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+// fedopt_step_kernel on 8 consecutive elements per thread (32-byte fp32 accesses of the bucket and the state,
+// 16-byte fp16 / 32-byte fp32 stores of the weights): bucket, x, m, v already offset to this buffer's part; n % 8 == 0
+// and aligned pointers (the launcher checks).  FedAvgM neither reads nor writes v.
+template <typename T>
+MF_DEV void fedopt8_body(const float* __restrict__ bucket, const FedOptHyper& h, float d, float votes,
+                         float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, T* __restrict__ p,
+                         T* __restrict__ g, int64_t n8, int64_t i) {
+  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, f32x8>::type;
+  if (i >= n8) return;
+  if (votes == 0.f) {
+    ((V*)p)[i] = ((const V*)g)[i];
+    return;
+  }
+  const bool adaptive = h.opt != FEDOPT_AVGM;
+  const f32x8 sv = ((const f32x8*)bucket)[i];
+  f32x8 xv = ((f32x8*)x)[i], mv = ((f32x8*)m)[i], vv = adaptive ? ((f32x8*)v)[i] : f32x8{};
+  const float omb1 = 1.f - h.b1, omb2 = 1.f - h.b2;
+  V out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float xe = xv[e], me = mv[e], ve = vv[e];
+    fedopt_elem(h, omb1, omb2, sv[e], d, xe, me, ve);
+    xv[e] = xe;
+    mv[e] = me;
+    vv[e] = ve;
+    out[e] = (T)(f16)xe;
+  }
+  ((f32x8*)x)[i] = xv;
+  ((f32x8*)m)[i] = mv;
+  if (adaptive) ((f32x8*)v)[i] = vv;
+  ((V*)p)[i] = out;
+  ((V*)g)[i] = out;
+}
+
+// both flat buffers in one launch, split as sgd8_both_kernel splits them: blocks [0, nb16) the fp16 trainables
+__global__ void fedopt8_step_kernel(const float* __restrict__ bucket, int weighted, FedOptHyper h,
+                                    float* __restrict__ x, float* __restrict__ m, float* __restrict__ v,
+                                    f16* __restrict__ p16, int64_t n16, float* __restrict__ p32, int64_t n32,
+                                    f16* __restrict__ g16, float* __restrict__ g32, unsigned nb16) {
+  const int64_t n = n16 + n32;
+  const float d = bucket[n], votes = bucket[n + weighted];
+  if (blockIdx.x < nb16)
+    fedopt8_body<f16>(bucket, h, d, votes, x, m, v, p16, g16, n16 / 8,
+                      (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+  else
+    fedopt8_body<float>(bucket + n16, h, d, votes, x + n16, m + n16, v ? v + n16 : v, p32, g32, n32 / 8,
+                        (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x);
+}
+
+// fp16(x) into another client's trainables and global copy (the rank's second and later clients)
+__global__ void fedopt_deliver_kernel(const float* __restrict__ x, f16* __restrict__ p16, int64_t n16,
+                                      float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
+                                      float* __restrict__ g32) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n16 + n32) return;
+  const f16 val = (f16)x[i];
+  if (i < n16) {
+    p16[i] = val;
+    g16[i] = val;
+  } else {
+    p32[i - n16] = (float)val;
+    g32[i - n16] = (float)val;
+  }
+}
+
+template <typename T>
+MF_DEV void deliver8_body(const float* __restrict__ x, T* __restrict__ p, T* __restrict__ g, int64_t n8, int64_t i) {
+  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, f32x8>::type;
+  if (i >= n8) return;
+  const f32x8 xv = ((const f32x8*)x)[i];
+  V out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = (T)(f16)xv[e];
+  ((V*)p)[i] = out;
+  ((V*)g)[i] = out;
+}
+
+__global__ void fedopt8_deliver_kernel(const float* __restrict__ x, f16* __restrict__ p16, int64_t n16,
+                                       float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
+                                       float* __restrict__ g32, unsigned nb16) {
+  if (blockIdx.x < nb16)
+    deliver8_body<f16>(x, p16, g16, n16 / 8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+  else
+    deliver8_body<float>(x + n16, p32, g32, n32 / 8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x);
+}
+
 // out[i] = (((g_0[i] + g_1[i]) + g_2[i]) + ...) in client order, g_c = gathered + c * stride: the
 // per-key torch.stack(...) sum of trainers/maple_fed.py:311-314 in the order the reference stacks its
 // clients, whatever order the collective delivered them in (8 floats per thread, fp32 accumulation)
@@ -578,6 +747,60 @@ extern "C" int mf_fedavg_unpack(const float* bucket, void* p16, int64_t n16, flo
                                 float* g32, void* stream) {
   if (n16 + n32 <= 0) return 0;
   unpack_kernel<<<nblk(n16 + n32), 256, 0, (hipStream_t)stream>>>(bucket, (f16*)p16, n16, p32, n32, (f16*)g16, g32);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// The FedOpt server step on the summed bucket (weighted = 0: [sum | votes], 1: [sum | wsum | votes]), one launch
+// over n16 + n32 elements.  opt: 1 fedavgm, 2 fedadagrad, 3 fedadam, 4 fedyogi; v is unused (may be null) for 1.
+extern "C" int mf_fedopt_step(const float* bucket, int weighted, int opt, float beta1, float beta2, float tau,
+                              float eta, float* x, float* m, float* v, void* p16, int64_t n16, float* p32,
+                              int64_t n32, void* g16, float* g32, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedopt_step: negative size", -1);
+  if (opt < FEDOPT_AVGM || opt > FEDOPT_YOGI) return mf_set_error("mf_fedopt_step: unknown optimizer id", -1);
+  if (weighted != 0 && weighted != 1) return mf_set_error("mf_fedopt_step: weighted is 0 or 1", -1);
+  const bool adaptive = opt != FEDOPT_AVGM;
+  if (!__builtin_isfinite(beta1) || !__builtin_isfinite(beta2) || !__builtin_isfinite(tau) ||
+      !__builtin_isfinite(eta))
+    return mf_set_error("mf_fedopt_step: non-finite hyper-parameter", -1);
+  if (adaptive && !(tau > 0.f)) return mf_set_error("mf_fedopt_step: tau <= 0 for an adaptive optimizer", -1);
+  if (!x || !m || (adaptive && !v)) return mf_set_error("mf_fedopt_step: null state pointer", -1);
+  if (n16 + n32 == 0) return 0;
+  if (!bucket || (n16 > 0 && (!p16 || !g16)) || (n32 > 0 && (!p32 || !g32)))
+    return mf_set_error("mf_fedopt_step: null bucket, weights or global copy", -1);
+  hipStream_t st = (hipStream_t)stream;
+  const FedOptHyper h{opt, beta1, beta2, tau, eta};
+  auto al = [](const void* p, uintptr_t a) { return (uintptr_t)p % a == 0; };
+  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && al(bucket, 32) && al(x, 32) && al(m, 32) &&
+                   (!adaptive || al(v, 32)) && al(p16, 16) && al(g16, 16) && al(p32, 32) && al(g32, 32);
+  if (vec) {
+    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
+    fedopt8_step_kernel<<<nb16 + nb32, 256, 0, st>>>(bucket, weighted, h, x, m, adaptive ? v : nullptr, (f16*)p16, n16,
+                                                     p32, n32, (f16*)g16, g32, nb16);
+  } else {
+    fedopt_step_kernel<<<nblk(n16 + n32), 256, 0, st>>>(bucket, weighted, h, x, m, v, (f16*)p16, n16, p32, n32,
+                                                        (f16*)g16, g32);
+  }
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* p32, int64_t n32, void* g16,
+                                 float* g32, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedopt_deliver: negative size", -1);
+  if (!x) return mf_set_error("mf_fedopt_deliver: null state pointer", -1);
+  if (n16 + n32 == 0) return 0;
+  if ((n16 > 0 && (!p16 || !g16)) || (n32 > 0 && (!p32 || !g32)))
+    return mf_set_error("mf_fedopt_deliver: null weights or global copy", -1);
+  hipStream_t st = (hipStream_t)stream;
+  auto al = [](const void* p, uintptr_t a) { return (uintptr_t)p % a == 0; };
+  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && al(x, 32) && al(p16, 16) && al(g16, 16) && al(p32, 32) && al(g32, 32);
+  if (vec) {
+    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
+    fedopt8_deliver_kernel<<<nb16 + nb32, 256, 0, st>>>(x, (f16*)p16, n16, p32, n32, (f16*)g16, g32, nb16);
+  } else {
+    fedopt_deliver_kernel<<<nblk(n16 + n32), 256, 0, st>>>(x, (f16*)p16, n16, p32, n32, (f16*)g16, g32);
+  }
   MF_CHECK_LAUNCH();
   return 0;
 }

@@ -46,6 +46,20 @@ weight=w packs [w * trainables | w | vote] (mf_fedavg_pack_weighted), the exchan
 it sums the n + 1 of the plain layout, and unpack divides by the summed weights (mf_fedavg_unpack_weighted).  The
 fp32 products are rounded in the pack kernel and summed in client order, so the "ordered" result equals the torch
 expression acc = w0*x0; acc += wc*xc ...; (acc / sum w).half() bit for bit at any world size.
+
+FedOpt server optimizers (FED.SERVER_OPT, off by default): FedAvgM (Hsu et al., 2019) and FedAdagrad / FedAdam /
+FedYogi (Reddi et al., ICLR 2021, Algorithm 2).  The global weights are fp16, and a server step
+eta * m / (sqrt(v) + tau) with a small eta moves hardly any fp16 weight, so ServerOptimizer keeps an fp32 master
+copy x of the trainables with the moments m and v, and the clients receive fp16(x).  The step runs in the kernel
+that otherwise turns the summed bucket into weights (mf_fedopt_step in mf_fedavg_unpack's place: no host
+synchronisation, no extra pass): the round's (weighted) mean is the pseudo-gradient's target, delta = mean - x.  One
+ServerOptimizer per process serves all of the rank's buckets; the first unpack() after the rank's packs applies the
+step and writes that client, the others receive the same fp16(x) (mf_fedopt_deliver), so the step runs exactly once
+per completed exchange -- also after a late-failure re-exchange, which packs again before any unpack.  Every rank
+applies the step to the same total (each holds the whole summed bucket after either exchange mode, and at world
+size 1) with the same kernel, so the replicated states stay bit-identical across the ranks without a further
+collective.  A round without a valid client leaves x, m, v untouched.  An x outside the fp16 range is delivered as
++-inf, and the next round's validity scan then excludes every client.
 """
 from __future__ import annotations
 
@@ -72,6 +86,80 @@ class _HipKernels:
     fedavg_pack_weighted = staticmethod(ops.fedavg_pack_weighted)
     fedavg_unpack_weighted = staticmethod(ops.fedavg_unpack_weighted)
     fedavg_reduce_ordered = staticmethod(ops.fedavg_reduce_ordered)
+    fedopt_step = staticmethod(ops.fedopt_step)
+    fedopt_deliver = staticmethod(ops.fedopt_deliver)
+
+
+SERVER_OPTS = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
+
+
+class ServerOptimizer:
+    """The FedOpt server state of one process, shared by the rank's buckets (module docstring): the fp32 master copy
+    x of the trainables ([fp16 trainables | fp32 trainables], the bucket's order), the first moment m and, for the
+    adaptive optimizers, the second moment v.  x = float(global copy), m = 0, v = tau * tau (an fp32 product;
+    Reddi et al. require v_{-1} >= tau^2) until a round completes.  FedAvgM has no v."""
+
+    def __init__(self, name: str, engine, lr: float = 1.0, beta1: float = 0.9, beta2: float = 0.99,
+                 tau: float = 1e-3):
+        if name not in SERVER_OPTS:
+            raise ValueError(f"server optimizer {name!r}: one of {SERVER_OPTS}")
+        lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
+        if not math.isfinite(lr) or lr < 0.0:
+            raise ValueError(f"server learning rate {lr}: finite and >= 0")
+        for label, b in (("momentum (beta1)", beta1), ("beta2", beta2)):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"server {label} {b}: in [0, 1)")
+        self.adaptive = name != "fedavgm"
+        if not math.isfinite(tau) or (self.adaptive and tau <= 0.0):
+            raise ValueError(f"server tau {tau}: finite and > 0")
+        self.name, self.lr, self.beta1, self.beta2, self.tau = name, lr, beta1, beta2, tau
+        # engine: what FedAvgBucket needs (n16, n32, flat16, flat32), holding the initial global weights
+        self.n16, self.n32 = engine.n16, engine.n32
+        n, dev = self.n16 + self.n32, engine.flat16.device
+        self.x = torch.empty(n, device=dev, dtype=torch.float32)
+        self.m = torch.empty(n, device=dev, dtype=torch.float32)
+        self.v = torch.empty(n, device=dev, dtype=torch.float32) if self.adaptive else None
+        self.pending = False  # a pack since the last step: the next unpack applies the step, the others deliver
+        self._reset(engine.flat16, engine.flat32)
+
+    def hyper(self) -> dict:
+        return {"lr": self.lr, "beta1": self.beta1, "beta2": self.beta2, "tau": self.tau}
+
+    def reset_from(self, bucket: "FedAvgBucket"):
+        """Restart from a bucket's global copy: x = its fp32 value, m = 0, v = tau * tau."""
+        if (bucket.e.n16, bucket.e.n32) != (self.n16, self.n32):
+            raise ValueError("ServerOptimizer.reset_from: a bucket of another size")
+        self._reset(bucket.global16, bucket.global32)
+
+    def _reset(self, g16, g32):
+        self.x[:self.n16].copy_(g16.detach())
+        self.x[self.n16:].copy_(g32.detach())
+        self.m.zero_()
+        if self.v is not None:
+            t = torch.tensor(self.tau, dtype=torch.float32)
+            self.v.fill_(float(t * t))
+
+    def state_dict(self) -> dict:
+        """CPU tensors and plain numbers only (torch.load(..., weights_only=True) reads it)."""
+        return {"name": self.name, "hyper": self.hyper(), "n16": self.n16, "n32": self.n32,
+                "x": self.x.detach().cpu().clone(), "m": self.m.detach().cpu().clone(),
+                "v": None if self.v is None else self.v.detach().cpu().clone()}
+
+    def load_state_dict(self, sd: dict):
+        """The moments and the master copy of a saved state; this optimizer's own hyper-parameters stay (they are
+        the run's configuration).  ValueError for another optimizer or other sizes."""
+        if sd.get("name") != self.name:
+            raise ValueError(f"server optimizer state of {sd.get('name')!r}, this one is {self.name!r}")
+        if (sd.get("n16"), sd.get("n32")) != (self.n16, self.n32):
+            raise ValueError(f"server optimizer state of sizes {(sd.get('n16'), sd.get('n32'))}, "
+                             f"this one has {(self.n16, self.n32)}")
+        keys = ("x", "m") + (("v",) if self.adaptive else ())
+        for k in keys:
+            t = sd.get(k)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != self.n16 + self.n32:
+                raise ValueError(f"server optimizer state: {k!r} is not fp32 of {self.n16 + self.n32} elements")
+        for k in keys:
+            getattr(self, k).copy_(sd[k].reshape(-1))
 
 
 def resolve_client_weights(spec, sample_counts: Sequence[int], num_clients: int) -> Optional[List[float]]:
@@ -128,7 +216,8 @@ class FedAvgBucket:
     exchange through one FedAvgExchange over all their buckets."""
 
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None, kernels=_HipKernels,
-                 mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None):
+                 mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None,
+                 server: Optional["ServerOptimizer"] = None):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         if weight is not None:
@@ -160,6 +249,9 @@ class FedAvgBucket:
         self.global16 = engine.flat16.detach().clone()
         self.global32 = engine.flat32.detach().clone()
         self._x: Optional[FedAvgExchange] = None
+        if server is not None and (server.n16, server.n32) != (engine.n16, engine.n32):
+            raise ValueError("FedAvgBucket: the server optimizer was built for other sizes")
+        self.server = server
 
     # -- per client
     def pack(self, failed: bool = False):
@@ -178,12 +270,25 @@ class FedAvgBucket:
             self.k.fedavg_pack(e.flat16, e.flat32, self.flag, self.buf)
         else:
             self.k.fedavg_pack_weighted(e.flat16, e.flat32, self.flag, self.weight, self.buf)
+        if self.server is not None:
+            self.server.pending = True  # a new exchange: its first unpack applies the server step
 
     def unpack(self):
         """The fp16-rounded mean into every trainable (device-side n_valid; n_valid == 0 leaves the weights
-        at the previous global copy).  No host synchronisation."""
+        at the previous global copy).  No host synchronisation.  With a server optimizer: the first unpack after
+        the rank's packs applies the server step to the summed bucket and writes this client; the other local
+        clients receive the same fp16(x) (deliver), so the step runs once per exchange -- a late-failure
+        re-exchange packs again before any unpack and changes nothing about that."""
         e = self.e
-        if self.weight is None:
+        sv = self.server
+        if sv is not None:
+            if sv.pending:
+                self.k.fedopt_step(self.buf, self.weight is not None, sv.name, sv.beta1, sv.beta2, sv.tau, sv.lr,
+                                   sv.x, sv.m, sv.v, e.flat16, e.flat32, self.global16, self.global32)
+                sv.pending = False
+            else:
+                self.k.fedopt_deliver(sv.x, e.flat16, e.flat32, self.global16, self.global32)
+        elif self.weight is None:
             self.k.fedavg_unpack(self.buf, e.flat16, e.flat32, self.global16, self.global32)
         else:
             self.k.fedavg_unpack_weighted(self.buf, e.flat16, e.flat32, self.global16, self.global32)
@@ -194,6 +299,8 @@ class FedAvgBucket:
         broadcast_weights: what an all-failed round reverts to)."""
         self.global16.copy_(self.e.flat16)
         self.global32.copy_(self.e.flat32)
+        if self.server is not None:
+            self.server.reset_from(self)
 
     def n_valid(self) -> int:
         """Valid clients of the last round (host sync)."""

@@ -715,6 +715,75 @@ def fedavg_unpack(bucket, p16, p32, g16=None, g32=None):
     call("mf_fedavg_unpack", _p(bucket), _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16), _p(g32), _s())
 
 
+FEDOPT_IDS = {"fedavgm": 1, "fedadagrad": 2, "fedadam": 3, "fedyogi": 4}
+
+
+def _overlap(a, b) -> bool:
+    if a is None or b is None or not a.numel() or not b.numel():
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _check_fedopt_outputs(p16, p32, g16, g32):
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    _check_flat("g16", g16, torch.float16, p16.numel())
+    _check_flat("g32", g32, torch.float32, p32.numel())
+    if _overlap(p16, g16) or _overlap(p32, g32):
+        raise ValueError("g16 / g32: buffers of their own required")
+
+
+def fedopt_step(bucket, weighted, opt, beta1, beta2, tau, eta, x, m, v, p16, p32, g16, g32):
+    """The FedOpt server step on the summed bucket (mf_fedopt_step).  opt: "fedavgm", "fedadagrad", "fedadam" or
+    "fedyogi"; x, m, v: fp32 state of n16 + n32 elements each (v is None for fedavgm), buffers of their own; bucket:
+    the plain (n + 1 floats) or, weighted=True, the weighted (n + 2 floats) layout."""
+    import math
+    if opt not in FEDOPT_IDS:
+        raise ValueError(f"opt: one of {tuple(FEDOPT_IDS)}, got {opt!r}")
+    adaptive = opt != "fedavgm"
+    hp = {"beta1": float(beta1), "beta2": float(beta2), "tau": float(tau), "eta": float(eta)}
+    for name, val in hp.items():
+        if not math.isfinite(val):
+            raise ValueError(f"{name}: finite required, got {val}")
+    if adaptive and hp["tau"] <= 0.0:
+        raise ValueError(f"tau: > 0 required for {opt}, got {hp['tau']}")
+    _check_fedopt_outputs(p16, p32, g16, g32)
+    n = p16.numel() + p32.numel()
+    tail = 2 if weighted else 1
+    if bucket.dtype != torch.float32 or not bucket.is_contiguous() or bucket.numel() < n + tail:
+        raise ValueError(f"bucket: contiguous fp32 of at least n16 + n32 + {tail} floats required")
+    if x is None or m is None or (adaptive and v is None):
+        raise ValueError("x, m" + (", v" if adaptive else "") + ": the server state is required")
+    state = [("x", x), ("m", m)] + ([("v", v)] if adaptive else [])
+    for name, t in state:
+        _check_flat(name, t, torch.float32, n)
+    others = [("bucket", bucket[:n + tail]), ("p16", p16), ("p32", p32), ("g16", g16), ("g32", g32)]
+    for i, (name, t) in enumerate(state):
+        for oname, o in state[i + 1:] + others:
+            if _overlap(t, o):
+                raise ValueError(f"{name}: a buffer of its own required (it overlaps {oname})")
+    # bucket read; x, m (, v) read and written; the weights and the global copy written
+    nb = n * (4.0 + 8.0 * len(state)) + p16.numel() * 4.0 + p32.numel() * 8.0
+    ev = _hbm(f"fedopt_step/{opt}", nb)
+    call("mf_fedopt_step", _p(bucket), int(bool(weighted)), FEDOPT_IDS[opt], hp["beta1"], hp["beta2"], hp["tau"],
+         hp["eta"], _p(x), _p(m), _p(v) if adaptive else None, _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16),
+         _p(g32), _s())
+    _rec(ev)
+
+
+def fedopt_deliver(x, p16, p32, g16, g32):
+    """fp16(x) into another client's trainables and global copy (mf_fedopt_deliver); x is only read."""
+    _check_fedopt_outputs(p16, p32, g16, g32)
+    if x is None:
+        raise ValueError("x: the server state is required")
+    _check_flat("x", x, torch.float32, p16.numel() + p32.numel())
+    for oname, o in (("p16", p16), ("p32", p32), ("g16", g16), ("g32", g32)):
+        if _overlap(x, o):
+            raise ValueError(f"x: a buffer of its own required (it overlaps {oname})")
+    call("mf_fedopt_deliver", _p(x), _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16), _p(g32), _s())
+
+
 def fedavg_reduce_ordered(gathered, nclients, out):
     """out = sum over clients (in client order) of gathered.view(nclients, -1)[:, :out.numel()]."""
     stride = gathered.numel() // nclients

@@ -22,6 +22,7 @@ ValueError (trainers/maple.py:526-535, not caught); kernel failures -> RuntimeEr
 from __future__ import annotations
 
 import dataclasses
+import math
 import os
 import os.path as osp
 import time
@@ -33,7 +34,8 @@ import torch.distributed as dist
 from . import ops
 from .data import DATASET_CLASSES, SyntheticClientDataManager, unified_classnames
 from .engine import EngineConfig, MapleEngine
-from .federated import FedAvgBucket, FedAvgExchange, FederatedAbort, resolve_client_weights
+from .federated import (SERVER_OPTS, FedAvgBucket, FedAvgExchange, FederatedAbort, ServerOptimizer,
+                        resolve_client_weights)
 from .captions import caption_tokens, draw_caption_weights, has_captions
 from .modules import CustomCLIP
 from .schedule import HostLR
@@ -589,14 +591,45 @@ class MaPLeFederated(TrainerX):
         dist.all_gather_object(gathered, local)
         return [n for part in gathered for n in part]
 
+    def _server_opt_cfg(self, get):
+        """FED.SERVER_OPT and its numbers, validated: ("none" | the optimizer's name, {key: value}).  ValueError
+        naming the key for an unknown optimizer, a beta outside [0, 1), eta < 0 or non-finite, tau <= 0."""
+        name = get("SERVER_OPT", "none")
+        name = name.strip().lower() if isinstance(name, str) else name
+        if name != "none" and name not in SERVER_OPTS:
+            raise ValueError(f"FED.SERVER_OPT {name!r}: one of {('none',) + SERVER_OPTS}")
+        hp = {}
+        for key, default in (("SERVER_LR", 1.0), ("SERVER_MOMENTUM", 0.9), ("SERVER_BETA2", 0.99),
+                             ("SERVER_TAU", 1e-3)):
+            try:
+                hp["FED." + key] = float(get(key, default))
+            except (TypeError, ValueError):
+                raise ValueError(f"FED.{key} {get(key, default)!r}: a number") from None
+        eta, tau = hp["FED.SERVER_LR"], hp["FED.SERVER_TAU"]
+        if not math.isfinite(eta) or eta < 0.0:
+            raise ValueError(f"FED.SERVER_LR {eta}: the server learning rate is finite and >= 0")
+        for key in ("FED.SERVER_MOMENTUM", "FED.SERVER_BETA2"):
+            if not 0.0 <= hp[key] < 1.0:
+                raise ValueError(f"{key} {hp[key]}: in [0, 1)")
+        if not math.isfinite(tau) or tau <= 0.0:
+            raise ValueError(f"FED.SERVER_TAU {tau}: finite and > 0")
+        if name != "none" and self.rank == 0:
+            line = f"[INFO] Server optimizer: {name}, eta = {eta:g}, beta1 = {hp['FED.SERVER_MOMENTUM']:g}"
+            if name != "fedavgm":
+                line += f", beta2 = {hp['FED.SERVER_BETA2']:g}, tau = {tau:g}"
+            print(line)
+        return name, hp
+
     def build_model(self):
-        """trainers/maple_fed.py:164-176, plus the two options the reference lacks (both off by default):
-        FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.) and FED.PROX_MU (FedProx, Li et al.)."""
+        """trainers/maple_fed.py:164-176, plus the options the reference lacks (all off by default):
+        FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.) and
+        FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
         if mu < 0.0 or mu != mu:
             raise ValueError(f"FED.PROX_MU {mu}: the FedProx coefficient is >= 0 (0 = off)")
+        server_opt, server_hp = self._server_opt_cfg(get)
         spec = get("CLIENT_WEIGHTS", "uniform")
         self.client_weights = resolve_client_weights(spec, self._client_sample_counts(spec), self.num_clients)
         if self.client_weights is not None and self.rank == 0:
@@ -611,8 +644,12 @@ class MaPLeFederated(TrainerX):
         self.register_model("MultiModalPromptLearner_Aggregator", c0.model, None, None)
         mode = get("AGGREGATION", "ordered")
         cw = self.client_weights
-        self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id])
-                    for c in self.clients]
+        # one server optimizer per process, shared by the rank's buckets (every client starts from the same weights)
+        self.server = None if server_opt == "none" else ServerOptimizer(
+            server_opt, c0.engine, lr=server_hp["FED.SERVER_LR"], beta1=server_hp["FED.SERVER_MOMENTUM"],
+            beta2=server_hp["FED.SERVER_BETA2"], tau=server_hp["FED.SERVER_TAU"])
+        self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id],
+                                 server=self.server) for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode)
         if mu > 0.0:
             # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
@@ -795,6 +832,11 @@ class MaPLeFederated(TrainerX):
             c.engine.reset_momentum()
             c.optim.rebuild(getattr(c, "epoch", None))
             c.sched = c.optim.sched
+        if global_sd is not None and getattr(self, "server", None) is not None:
+            # weights from outside the round loop: the server optimizer restarts from them (x = their fp32 value,
+            # moments cleared), and the buckets' global copies follow so that x and the copies stay one model
+            for fed in self.fed:
+                fed.snapshot()
 
     def finalize_training(self):
         print("\nTraining Summary:")
@@ -814,8 +856,11 @@ class MaPLeFederated(TrainerX):
         target = osp.join(directory, "MultiModalPromptLearner_Aggregator")
         os.makedirs(target, exist_ok=True)
         sd = {k: v.detach().half().cpu() for k, v in self.clients[0].model.state_dict().items()}
+        server = getattr(self, "server", None)
         ckpt = {"epoch": self.cfg.OPTIM.MAX_EPOCH, "state_dict": sd, "optimizer": None, "scheduler": None,
-                "val_result": val_result, "cfg": self.cfg.dump()}
+                "val_result": val_result, "cfg": self.cfg.dump(),
+                # the FedOpt server state (fp32 master copy and moments; CPU tensors and numbers); None when off
+                "server_optimizer": None if server is None else server.state_dict()}
         fpath = osp.join(target, f"model.pth.tar-{self.cfg.OPTIM.MAX_EPOCH}")
         torch.save(ckpt, fpath)
         with open(osp.join(target, "checkpoint"), "w") as f:
@@ -840,6 +885,11 @@ class MaPLeFederated(TrainerX):
             self.broadcast_weights(self.global_weights)
             for fed in getattr(self, "fed", []):
                 fed.snapshot()  # an all-failed round now reverts to the loaded weights
+            # ... and the server optimizer starts from them, unless the checkpoint carries its state
+            server = getattr(self, "server", None)
+            if server is not None and ckpt.get("server_optimizer") is not None:
+                server.load_state_dict(ckpt["server_optimizer"])
+                print(f"Restored the {server.name} server optimizer state.")
             print("Broadcasted loaded global weights.")
         else:
             print("Warning: loaded global weights invalid! Skipping broadcast.")

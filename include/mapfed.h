@@ -255,6 +255,37 @@ int mf_fedavg_pack(const void* p16, int64_t n16, const float* p32, int64_t n32, 
                    float* bucket, void* stream);
 int mf_fedavg_unpack(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
                      void* stream);
+/* FedOpt server optimizers, applied to the summed bucket in mf_fedavg_unpack's place: FedAvgM (Hsu, Qi, Brown:
+ * "Measuring the Effects of Non-Identical Data Distribution for Federated Visual Classification", 2019) and
+ * FedAdagrad / FedAdam / FedYogi (Reddi et al.: "Adaptive Federated Optimization", ICLR 2021, Algorithm 2; no bias
+ * correction).  opt: 1 fedavgm, 2 fedadagrad, 3 fedadam, 4 fedyogi.  bucket is the sum over the clients in the
+ * plain layout (weighted = 0: n floats, then the vote count) or the weighted one (weighted = 1: n floats, the summed
+ * weights, the vote count), n = n16 + n32.  x, m, v: the server's fp32 master copy of the trainables and its two
+ * moments, n floats each in the bucket's order [fp16 trainables | fp32 trainables]; v is neither read nor written
+ * by fedavgm (may be null).  Rounding points: per element every binary operation below is one IEEE fp32 operation
+ * (round to nearest even, no fused multiply-add); beta1, beta2, tau, eta are fp32 and 1 - beta1, 1 - beta2 are fp32
+ * differences formed in the kernel; division and sqrtf are correctly rounded:
+ *   d = bucket[n];  mean = bucket[i] / d;  delta = mean - x
+ *   fedavgm:    m = beta1*m + delta;                                upd = m
+ *   adaptive:   m = beta1*m + (1-beta1)*delta;  s = delta*delta
+ *     fedadagrad: v = v + s
+ *     fedadam:    v = beta2*v + (1-beta2)*s
+ *     fedyogi:    v = v - ((1-beta2)*s) * sign(v - s),  sign(0) = 0
+ *                                                                   upd = m / (sqrtf(v) + tau)
+ *   x = x + eta*upd;  val = fp16(x);  p16 = g16 = val;  p32 = g32 = float(val)
+ * so the clients receive what a `.half()` state dict would hold (mf_fedavg_unpack's contract, the fp32 LayerNorm
+ * parameters and logit_scale included) and only x is fp32.  A vote count of 0 restores the trainables from g16 / g32
+ * and leaves x, m, v untouched.  An x outside the fp16 range is delivered as +-inf.  8 elements per thread when
+ * n16 % 8 == n32 % 8 == 0 and the pointers are 32-byte aligned (16 for p16 / g16), one per thread otherwise; the
+ * same bits either way.  x, m, v, the bucket and the weight buffers must not overlap.  Errors: negative sizes, an
+ * unknown opt, a non-finite hyper-parameter, tau <= 0 for an adaptive optimizer, a null state pointer.            */
+int mf_fedopt_step(const float* bucket, int weighted, int opt, float beta1, float beta2, float tau, float eta,
+                   float* x, float* m, float* v, void* p16, int64_t n16, float* p32, int64_t n32, void* g16,
+                   float* g32, void* stream);
+/* val = fp16(x) into another client's trainables and global copy (p16 = g16 = val, p32 = g32 = float(val)): the
+ * second and later clients of a rank after mf_fedopt_step wrote the first.  Changes no state.                    */
+int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
+                      void* stream);
 /* FedAvg in client order (trainers/maple_fed.py:311-314: torch.stack over the clients, then mean):   */
 /* out[i] = sum_c gathered[c * stride + i] accumulated c = 0, 1, ... in fp32, for i < n; gathered    */
 /* holds every client's packed bucket (an all-gather of mf_fedavg_pack outputs)                      */
