@@ -21,6 +21,14 @@ namespace {
 
 constexpr int CHUNK = 8192;
 
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+// 8 consecutive elements of a flat buffer: one 16-byte (fp16) or two 16-byte (fp32) accesses
+template <typename T>
+using vec8 = typename std::conditional<std::is_same<T, f16>::value, f16x8, f32x8>::type;
+
+inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+inline bool aligned(const void* p, uintptr_t bytes) { return (uintptr_t)p % bytes == 0; }
+
 struct Chunk {
   int seg;
   int is16;
@@ -150,87 +158,27 @@ __global__ __launch_bounds__(1024) void clip_coef_kernel(const float* __restrict
 // device memory so a captured step replays with the current schedule value.  halt != 0 (a non-finite loss
 // earlier in the epoch or in this step) leaves parameters, gradients and momentum untouched: the reference
 // raises at the first non-finite loss before its backward (trainers/maple.py:375-376), so no update follows.
-template <typename T>
-__global__ void sgd_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, int64_t n,
-                           const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || hyper[4] != 0.f) return;
-  const float coef = coef_ptr[1];
-  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2];
-  const bool first = hyper[3] != 0.f;
-  const float pv = (float)p[i];
-  const float gc = (float)(T)mul32((float)g[i], coef);
-  g[i] = (T)gc;
-  const float dp = (float)(T)(gc + wd * pv);
-  float b;
-  if (first)
-    b = dp;
-  else
-    b = (float)(T)((float)(T)mul32((float)buf[i], momentum) + dp);
-  buf[i] = (T)b;
-  p[i] = (T)(pv + (-lr) * b);
-}
-
-// sgd_kernel on 8 consecutive elements per thread (16-byte fp16 / 2 x 16-byte fp32 accesses), the same
-// per-element arithmetic; n % 8 == 0 and 16-byte aligned buffers
-template <typename T>
-MF_DEV void sgd8_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, int64_t n8, int64_t i,
-                      const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
-  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, float __attribute__((ext_vector_type(8)))>::type;
-  if (i >= n8 || hyper[4] != 0.f) return;
-  const float coef = coef_ptr[1];
-  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2];
-  const bool first = hyper[3] != 0.f;
-  V pv = ((V*)p)[i], gv = ((V*)g)[i], bv = first ? V{} : ((V*)buf)[i];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float pe = (float)pv[e];
-    const float gc = (float)(T)mul32((float)gv[e], coef);
-    gv[e] = (T)gc;
-    const float dp = (float)(T)(gc + wd * pe);
-    float b;
-    if (first)
-      b = dp;
-    else
-      b = (float)(T)((float)(T)mul32((float)bv[e], momentum) + dp);
-    bv[e] = (T)b;
-    pv[e] = (T)(pe + (-lr) * b);
-  }
-  ((V*)g)[i] = gv;
-  ((V*)buf)[i] = bv;
-  ((V*)p)[i] = pv;
-}
-
-template <typename T>
-__global__ void sgd8_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, int64_t n8,
-                            const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
-  sgd8_body<T>(p, g, buf, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
-}
-
-// both flat buffers' SGD in one launch: blocks [0, nb16) update the fp16 trainables, the rest the fp32 ones
-__global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f16* __restrict__ b16, int64_t n16_8,
-                                 float* __restrict__ p32, float* __restrict__ g32, float* __restrict__ b32,
-                                 int64_t n32_8, unsigned nb16, const float* __restrict__ coef_ptr,
-                                 const float* __restrict__ hyper) {
-  if (blockIdx.x < nb16)
-    sgd8_body<f16>(p16, g16, b16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
-  else
-    sgd8_body<float>(p32, g32, b32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x, coef_ptr, hyper);
-}
-
+//
 // FedProx (Li et al., "Federated Optimization in Heterogeneous Networks", MLSys 2020): the local objective gains
 // (mu/2) * ||w - w_global||^2, whose gradient mu * (w - w_global) joins the clipped gradient in the optimizer, as
 // weight decay does.  hyper = {lr, momentum, weight_decay, first_step, halt, mu}.  Every line rounded to T, as
 // torch ops on T tensors round: gc = T(g*coef) (stored back: the stored gradient stays the clipped model
-// gradient); d = T(p - pglob); gp = T(gc + mu*d); d_p = T(gp + wd*p); momentum and parameter update as sgd_kernel.
-// pglob is read only and must not overlap p, g or buf.
-template <typename T>
-MF_DEV void sgd_prox_elem(float pe, float ge, float be, float qe, float coef, float lr, float momentum, float wd,
-                          float mu, bool first, float& p_out, float& g_out, float& b_out) {
+// gradient); d = T(p - pglob); gp = T(gc + mu*d); d_p = T(gp + wd*p); momentum and parameter update as the plain
+// step.  pglob is read only and must not overlap p, g or buf.
+//
+// The plain and the proximal step are the two instantiations of one element function, one scalar kernel, one
+// 8-wide body and one fused kernel, so each rounding is written once.  PROX = false reads neither pglob (null)
+// nor hyper[5] (the plain callers' hyper has 5 floats).
+template <typename T, bool PROX>
+MF_DEV void sgd_elem(float pe, float ge, float be, float qe, float coef, float lr, float momentum, float wd,
+                     float mu, bool first, float& p_out, float& g_out, float& b_out) {
   const float gc = (float)(T)mul32(ge, coef);
   g_out = gc;
-  const float d = (float)(T)(pe - qe);
-  const float gp = (float)(T)(gc + mul32(mu, d));
+  float gp = gc;
+  if constexpr (PROX) {
+    const float d = (float)(T)(pe - qe);
+    gp = (float)(T)(gc + mul32(mu, d));
+  }
   const float dp = (float)(T)(gp + wd * pe);
   float b;
   if (first)
@@ -241,39 +189,38 @@ MF_DEV void sgd_prox_elem(float pe, float ge, float be, float qe, float coef, fl
   p_out = (float)(T)(pe + (-lr) * b);
 }
 
-template <typename T>
-__global__ void sgd_prox_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf,
-                                const T* __restrict__ pglob, int64_t n, const float* __restrict__ coef_ptr,
-                                const float* __restrict__ hyper) {
+template <typename T, bool PROX>
+__global__ void sgd_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
+                           int64_t n, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || hyper[4] != 0.f) return;
   const bool first = hyper[3] != 0.f;
-  float po, go, bo;
-  sgd_prox_elem<T>((float)p[i], (float)g[i], first ? 0.f : (float)buf[i], (float)pglob[i], coef_ptr[1], hyper[0],
-                   hyper[1], hyper[2], hyper[5], first, po, go, bo);
+  float qe = 0.f, po, go, bo;
+  if constexpr (PROX) qe = (float)pglob[i];
+  sgd_elem<T, PROX>((float)p[i], (float)g[i], first ? 0.f : (float)buf[i], qe, coef_ptr[1], hyper[0], hyper[1],
+                    hyper[2], PROX ? hyper[5] : 0.f, first, po, go, bo);
   g[i] = (T)go;
   buf[i] = (T)bo;
   p[i] = (T)po;
 }
 
-// sgd_prox_kernel on 8 consecutive elements per thread: sgd8_body's accesses plus one 16-byte (fp16) / 2 x 16-byte
-// (fp32) read of the global copy; n % 8 == 0 and 32-byte aligned buffers
-template <typename T>
-MF_DEV void sgd8_prox_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
-                           int64_t n8, int64_t i, const float* __restrict__ coef_ptr,
-                           const float* __restrict__ hyper) {
-  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, float __attribute__((ext_vector_type(8)))>::type;
+// sgd_kernel on 8 consecutive elements per thread (16-byte fp16 / 2 x 16-byte fp32 accesses, the proximal step one
+// more read of the global copy), the same per-element arithmetic; n % 8 == 0 and 32-byte aligned buffers
+template <typename T, bool PROX>
+MF_DEV void sgd8_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
+                      int64_t n8, int64_t i, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
+  using V = vec8<T>;
   if (i >= n8 || hyper[4] != 0.f) return;
   const float coef = coef_ptr[1];
-  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], mu = hyper[5];
+  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], mu = PROX ? hyper[5] : 0.f;
   const bool first = hyper[3] != 0.f;
-  V pv = ((V*)p)[i], gv = ((V*)g)[i], bv = first ? V{} : ((V*)buf)[i];
-  const V qv = ((const V*)pglob)[i];
+  V pv = ((V*)p)[i], gv = ((V*)g)[i], bv = first ? V{} : ((V*)buf)[i], qv{};
+  if constexpr (PROX) qv = ((const V*)pglob)[i];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     float po, go, bo;
-    sgd_prox_elem<T>((float)pv[e], (float)gv[e], (float)bv[e], (float)qv[e], coef, lr, momentum, wd, mu, first, po,
-                     go, bo);
+    sgd_elem<T, PROX>((float)pv[e], (float)gv[e], (float)bv[e], (float)qv[e], coef, lr, momentum, wd, mu, first, po,
+                      go, bo);
     gv[e] = (T)go;
     bv[e] = (T)bo;
     pv[e] = (T)po;
@@ -283,111 +230,103 @@ MF_DEV void sgd8_prox_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__
   ((V*)p)[i] = pv;
 }
 
-template <typename T>
-__global__ void sgd8_prox_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf,
-                                 const T* __restrict__ pglob, int64_t n8, const float* __restrict__ coef_ptr,
+template <typename T, bool PROX>
+__global__ void sgd8_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
+                            int64_t n8, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
+  sgd8_body<T, PROX>(p, g, buf, pglob, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+}
+
+// both flat buffers' SGD in one launch: blocks [0, nb16) update the fp16 trainables, the rest the fp32 ones
+template <bool PROX>
+__global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f16* __restrict__ b16,
+                                 const f16* __restrict__ q16, int64_t n16_8, float* __restrict__ p32,
+                                 float* __restrict__ g32, float* __restrict__ b32, const float* __restrict__ q32,
+                                 int64_t n32_8, unsigned nb16, const float* __restrict__ coef_ptr,
                                  const float* __restrict__ hyper) {
-  sgd8_prox_body<T>(p, g, buf, pglob, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
-}
-
-// both flat buffers' proximal SGD in one launch, split as sgd8_both_kernel splits them
-__global__ void sgd8_prox_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f16* __restrict__ b16,
-                                      const f16* __restrict__ q16, int64_t n16_8, float* __restrict__ p32,
-                                      float* __restrict__ g32, float* __restrict__ b32, const float* __restrict__ q32,
-                                      int64_t n32_8, unsigned nb16, const float* __restrict__ coef_ptr,
-                                      const float* __restrict__ hyper) {
   if (blockIdx.x < nb16)
-    sgd8_prox_body<f16>(p16, g16, b16, q16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+    sgd8_body<f16, PROX>(p16, g16, b16, q16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
   else
-    sgd8_prox_body<float>(p32, g32, b32, q32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x,
-                          coef_ptr, hyper);
+    sgd8_body<float, PROX>(p32, g32, b32, q32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x,
+                           coef_ptr, hyper);
 }
 
-// bucket[0:n16] = float(p16), bucket[n16:n16+n32] = p32
+// A client's bucket, plain: bucket[0:n16] = float(p16), bucket[n16:n] = p32 (n = n16 + n32), bucket[n] = 1, this
+// client's vote in the valid-client count.  Weighted, FedAvg as McMahan et al. define it ("Communication-Efficient
+// Learning of Deep Networks from Decentralized Data", AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The
+// client's weight travels in its bucket: bucket[0:n] = w * float(p) (the fp32 product is formed and stored here; the
+// sum is formed by reduce_ordered_kernel, so no fused multiply-add spans the two), bucket[n] = w, bucket[n+1] = 1
+// (its vote).  An invalid client (maple_fed.py:272-277) writes zeros everywhere.
+template <bool WEIGHTED>
+constexpr int TAIL = WEIGHTED ? 2 : 1;
+
+template <bool WEIGHTED>
 __global__ void pack_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32, int64_t n32,
-                            const int* __restrict__ invalid, float* __restrict__ bucket) {
+                            const int* __restrict__ invalid, float* __restrict__ bucket, float w) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool bad = invalid && invalid[0] != 0;  // this client's weights are excluded (maple_fed.py:272-277)
+  const int64_t n = n16 + n32;
+  const bool bad = invalid && invalid[0] != 0;
+  const auto weigh = [&](float x) {
+    if constexpr (WEIGHTED)
+      return w * x;
+    else
+      return x;
+  };
   if (i < n16)
-    bucket[i] = bad ? 0.f : (float)p16[i];
-  else if (i < n16 + n32)
-    bucket[i] = bad ? 0.f : p32[i - n16];
-  else if (i == n16 + n32)
-    bucket[i] = bad ? 0.f : 1.f;  // this client's vote in the valid-client count
+    bucket[i] = bad ? 0.f : weigh((float)p16[i]);
+  else if (i < n)
+    bucket[i] = bad ? 0.f : weigh(p32[i - n16]);
+  else if (i == n)
+    bucket[i] = bad ? 0.f : (WEIGHTED ? w : 1.f);
+  else if (WEIGHTED && i == n + 1)
+    bucket[i] = bad ? 0.f : 1.f;
 }
-// mean = sum / n_valid with n_valid = bucket[n16+n32] read on the device (no host sync); value =
-// fp16(mean); p16 = value, p32 = float(value)   (the `.half()` of trainers/maple_fed.py:314 followed
-// by load_state_dict into each parameter's dtype), and the value is kept as the new global copy
-// (g16/g32).  n_valid == 0 -> every client failed: the round is skipped and every client goes back
-// to the previous global weights (trainers/maple_fed.py:288-290 + the next round's broadcast).
+
+// fp16 `val` to element i of [fp16 trainables | fp32 trainables] and of the global copy (g16 / g32 may be null)
+MF_DEV void deliver(f16 val, int64_t i, f16* __restrict__ p16, int64_t n16, float* __restrict__ p32,
+                    f16* __restrict__ g16, float* __restrict__ g32) {
+  if (i < n16) {
+    p16[i] = val;
+    if (g16) g16[i] = val;
+  } else {
+    p32[i - n16] = (float)val;
+    if (g32) g32[i - n16] = (float)val;
+  }
+}
+// ... and the global copy's element i back into the trainables
+MF_DEV void restore(int64_t i, f16* __restrict__ p16, int64_t n16, float* __restrict__ p32,
+                    const f16* __restrict__ g16, const float* __restrict__ g32) {
+  if (i < n16) {
+    if (g16) p16[i] = g16[i];
+  } else {
+    if (g32) p32[i - n16] = g32[i - n16];
+  }
+}
+// the same for 8 consecutive elements of one buffer: fp16(x[e]), one 16-byte fp16 / 32-byte fp32 store each
+template <typename T>
+MF_DEV void deliver8(const f32x8& x, T* __restrict__ p, T* __restrict__ g, int64_t i) {
+  vec8<T> out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = (T)(f16)x[e];
+  ((vec8<T>*)p)[i] = out;
+  ((vec8<T>*)g)[i] = out;
+}
+
+// mean = sum / d with d = bucket[n] read on the device (no host sync): the valid-client count of the plain layout,
+// the summed weights of the weighted one; value = fp16(mean); p16 = value, p32 = float(value)   (the `.half()` of
+// trainers/maple_fed.py:314 followed by load_state_dict into each parameter's dtype), and the value is kept as the
+// new global copy (g16/g32).  No votes (bucket[n + TAIL - 1] == 0) -> every client failed: the round is skipped and
+// every client goes back to the previous global weights (trainers/maple_fed.py:288-290 + the next round's broadcast).
+template <bool WEIGHTED>
 __global__ void unpack_kernel(const float* __restrict__ bucket, f16* __restrict__ p16, int64_t n16,
                               float* __restrict__ p32, int64_t n32, f16* __restrict__ g16, float* __restrict__ g32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const float n_valid = bucket[n16 + n32];
-  if (i < n16) {
-    if (n_valid == 0.f) {
-      if (g16) p16[i] = g16[i];
-    } else {
-      const f16 v = (f16)(bucket[i] / n_valid);
-      p16[i] = v;
-      if (g16) g16[i] = v;
-    }
-  } else if (i < n16 + n32) {
-    const int64_t j = i - n16;
-    if (n_valid == 0.f) {
-      if (g32) p32[j] = g32[j];
-    } else {
-      const float v = r16(bucket[i] / n_valid);
-      p32[j] = v;
-      if (g32) g32[j] = v;
-    }
-  }
-}
-
-// FedAvg as McMahan et al. define it ("Communication-Efficient Learning of Deep Networks from Decentralized Data",
-// AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The client's weight travels in its bucket:
-// bucket[0:n] = w * float(p) (the fp32 product is formed and stored here; the sum is formed by
-// reduce_ordered_kernel, so no fused multiply-add spans the two), bucket[n] = w, bucket[n+1] = 1 (its vote);
-// an invalid client writes zeros everywhere.
-__global__ void pack_weighted_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32,
-                                     int64_t n32, const int* __restrict__ invalid, float w,
-                                     float* __restrict__ bucket) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool bad = invalid && invalid[0] != 0;
-  if (i < n16)
-    bucket[i] = bad ? 0.f : w * (float)p16[i];
-  else if (i < n16 + n32)
-    bucket[i] = bad ? 0.f : w * p32[i - n16];
-  else if (i == n16 + n32)
-    bucket[i] = bad ? 0.f : w;
-  else if (i == n16 + n32 + 1)
-    bucket[i] = bad ? 0.f : 1.f;
-}
-// unpack_kernel with the weighted layout: value = fp16(sum / sum of weights), the vote count at bucket[n+1];
-// no votes -> the previous global weights, as unpack_kernel
-__global__ void unpack_weighted_kernel(const float* __restrict__ bucket, f16* __restrict__ p16, int64_t n16,
-                                       float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
-                                       float* __restrict__ g32) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const float wsum = bucket[n16 + n32], n_valid = bucket[n16 + n32 + 1];
-  if (i < n16) {
-    if (n_valid == 0.f) {
-      if (g16) p16[i] = g16[i];
-    } else {
-      const f16 v = (f16)(bucket[i] / wsum);
-      p16[i] = v;
-      if (g16) g16[i] = v;
-    }
-  } else if (i < n16 + n32) {
-    const int64_t j = i - n16;
-    if (n_valid == 0.f) {
-      if (g32) p32[j] = g32[j];
-    } else {
-      const float v = r16(bucket[i] / wsum);
-      p32[j] = v;
-      if (g32) g32[j] = v;
-    }
-  }
+  const int64_t n = n16 + n32;
+  if (i >= n) return;
+  const float d = bucket[n], votes = bucket[n + TAIL<WEIGHTED> - 1];
+  if (votes == 0.f)
+    restore(i, p16, n16, p32, g16, g32);
+  else
+    deliver((f16)(bucket[i] / d), i, p16, n16, p32, g16, g32);
 }
 
 // FedOpt server optimizers: FedAvgM (Hsu, Qi, Brown: "Measuring the Effects of Non-Identical Data Distribution for
@@ -448,30 +387,15 @@ __global__ void fedopt_step_kernel(const float* __restrict__ bucket, int weighte
   const int64_t n = n16 + n32;
   if (i >= n) return;
   const float d = bucket[n], votes = bucket[n + weighted];
-  if (votes == 0.f) {
-    if (i < n16)
-      p16[i] = g16[i];
-    else
-      p32[i - n16] = g32[i - n16];
-    return;
-  }
+  if (votes == 0.f) return restore(i, p16, n16, p32, g16, g32);
   const bool adaptive = h.opt != FEDOPT_AVGM;
   float xe = x[i], me = m[i], ve = adaptive ? v[i] : 0.f;
   fedopt_elem(h, 1.f - h.b1, 1.f - h.b2, bucket[i], d, xe, me, ve);
   x[i] = xe;
   m[i] = me;
   if (adaptive) v[i] = ve;
-  const f16 val = (f16)xe;
-  if (i < n16) {
-    p16[i] = val;
-    g16[i] = val;
-  } else {
-    p32[i - n16] = (float)val;
-    g32[i - n16] = (float)val;
-  }
+  deliver((f16)xe, i, p16, n16, p32, g16, g32);
 }
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 // fedopt_step_kernel on 8 consecutive elements per thread (32-byte fp32 accesses of the bucket and the state,
 // 16-byte fp16 / 32-byte fp32 stores of the weights): bucket, x, m, v already offset to this buffer's part; n % 8 == 0
@@ -480,17 +404,15 @@ template <typename T>
 MF_DEV void fedopt8_body(const float* __restrict__ bucket, const FedOptHyper& h, float d, float votes,
                          float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, T* __restrict__ p,
                          T* __restrict__ g, int64_t n8, int64_t i) {
-  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, f32x8>::type;
   if (i >= n8) return;
   if (votes == 0.f) {
-    ((V*)p)[i] = ((const V*)g)[i];
+    ((vec8<T>*)p)[i] = ((const vec8<T>*)g)[i];
     return;
   }
   const bool adaptive = h.opt != FEDOPT_AVGM;
   const f32x8 sv = ((const f32x8*)bucket)[i];
   f32x8 xv = ((f32x8*)x)[i], mv = ((f32x8*)m)[i], vv = adaptive ? ((f32x8*)v)[i] : f32x8{};
   const float omb1 = 1.f - h.b1, omb2 = 1.f - h.b2;
-  V out;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     float xe = xv[e], me = mv[e], ve = vv[e];
@@ -498,13 +420,11 @@ MF_DEV void fedopt8_body(const float* __restrict__ bucket, const FedOptHyper& h,
     xv[e] = xe;
     mv[e] = me;
     vv[e] = ve;
-    out[e] = (T)(f16)xe;
   }
   ((f32x8*)x)[i] = xv;
   ((f32x8*)m)[i] = mv;
   if (adaptive) ((f32x8*)v)[i] = vv;
-  ((V*)p)[i] = out;
-  ((V*)g)[i] = out;
+  deliver8<T>(xv, p, g, i);
 }
 
 // both flat buffers in one launch, split as sgd8_both_kernel splits them: blocks [0, nb16) the fp16 trainables
@@ -527,27 +447,12 @@ __global__ void fedopt_deliver_kernel(const float* __restrict__ x, f16* __restri
                                       float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
                                       float* __restrict__ g32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n16 + n32) return;
-  const f16 val = (f16)x[i];
-  if (i < n16) {
-    p16[i] = val;
-    g16[i] = val;
-  } else {
-    p32[i - n16] = (float)val;
-    g32[i - n16] = (float)val;
-  }
+  if (i < n16 + n32) deliver((f16)x[i], i, p16, n16, p32, g16, g32);
 }
 
 template <typename T>
 MF_DEV void deliver8_body(const float* __restrict__ x, T* __restrict__ p, T* __restrict__ g, int64_t n8, int64_t i) {
-  using V = typename std::conditional<std::is_same<T, f16>::value, f16x8, f32x8>::type;
-  if (i >= n8) return;
-  const f32x8 xv = ((const f32x8*)x)[i];
-  V out;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) out[e] = (T)(f16)xv[e];
-  ((V*)p)[i] = out;
-  ((V*)g)[i] = out;
+  if (i < n8) deliver8<T>(((const f32x8*)x)[i], p, g, i);
 }
 
 __global__ void fedopt8_deliver_kernel(const float* __restrict__ x, f16* __restrict__ p16, int64_t n16,
@@ -595,7 +500,76 @@ __global__ void nonfinite_kernel(const void* __restrict__ x, int64_t n, int is16
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
-inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+// clip_grad_norm_ in two launches: the per-chunk partial sums, then the coefficient.  With a non-null hyper the
+// second also latches hyper[4] = max(hyper[4], *halt_src, *input_flag) for the SGD launch that follows (input_flag
+// may be null)
+int clip_launches(const void* g16, const float* g32, const void* chunks, int nchunks, float max_norm, float* part,
+                  float* out, float* hyper, const float* halt_src, const int* input_flag, hipStream_t st) {
+  if (nchunks > 0) {
+    sumsq_chunks_kernel<<<nchunks, 256, 0, st>>>((const f16*)g16, g32, (const Chunk*)chunks, part);
+    MF_CHECK_LAUNCH();
+  }
+  clip_coef_kernel<<<1, 1024, 0, st>>>(part, (const Chunk*)chunks, nchunks, max_norm, out, hyper, halt_src,
+                                       input_flag);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// SGD over one flat buffer: 8 elements per thread when the size and every pointer allow (a null pglob does), one
+// element per thread otherwise
+template <bool PROX>
+int sgd_step(void* p, void* g, void* buf, const void* pglob, int64_t n, int is16, const float* coef,
+             const float* hyper, hipStream_t st) {
+  if (n <= 0) return 0;
+  const bool vec = n % 8 == 0 && aligned(p, 32) && aligned(g, 32) && aligned(buf, 32) && aligned(pglob, 32);
+  if (vec && is16)
+    sgd8_kernel<f16, PROX><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n / 8, coef,
+                                                        hyper);
+  else if (vec)
+    sgd8_kernel<float, PROX><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob,
+                                                          n / 8, coef, hyper);
+  else if (is16)
+    sgd_kernel<f16, PROX><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n, coef, hyper);
+  else
+    sgd_kernel<float, PROX><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, n, coef,
+                                                     hyper);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// The whole optimizer step in three launches: clip_launches (the latch replaces the two torch.maximum launches the
+// engine used to make, at the step's start for the input check and here for the loss), then SGD over the fp16 and the
+// fp32 flat buffers in one launch.  Bit-identical to mf_clip_grad_norm + two mf_sgd_step (PROX: mf_sgd_prox_step; the
+// clip norm is the model gradient's, without the proximal term).
+template <bool PROX>
+int optimizer_step(void* p16, void* g16, void* b16, const void* glob16, int64_t n16, float* p32, float* g32,
+                   float* b32, const float* glob32, int64_t n32, const void* chunks, int nchunks, float max_norm,
+                   float* part, float* out, float* hyper, const float* halt_src, const int* input_flag,
+                   hipStream_t st) {
+  int rc = clip_launches(g16, g32, chunks, nchunks, max_norm, part, out, hyper, halt_src, input_flag, st);
+  if (rc) return rc;
+  const bool vec16 = n16 % 8 == 0 && aligned(p16, 32) && aligned(g16, 32) && aligned(b16, 32) && aligned(glob16, 32);
+  const bool vec32 = n32 % 8 == 0 && aligned(p32, 32) && aligned(g32, 32) && aligned(b32, 32) && aligned(glob32, 32);
+  if (vec16 && vec32 && n16 + n32 > 0) {
+    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
+    sgd8_both_kernel<PROX><<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, (const f16*)glob16, n16 / 8,
+                                                        p32, g32, b32, glob32, n32 / 8, nb16, out, hyper);
+    MF_CHECK_LAUNCH();
+    return 0;
+  }
+  rc = sgd_step<PROX>(p16, g16, b16, glob16, n16, 1, out, hyper, st);
+  return rc ? rc : sgd_step<PROX>(p32, g32, b32, glob32, n32, 0, out, hyper, st);
+}
+
+template <bool WEIGHTED>
+int fedavg_unpack(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
+                  void* stream) {
+  if (n16 + n32 <= 0) return 0;
+  unpack_kernel<WEIGHTED><<<nblk(n16 + n32), 256, 0, (hipStream_t)stream>>>(bucket, (f16*)p16, n16, p32, n32,
+                                                                            (f16*)g16, g32);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
 
 }  // namespace
 
@@ -606,60 +580,13 @@ extern "C" int mf_optim_chunk_elems() { return CHUNK; }
 // out: 3 floats (total norm, coef, finite flag)
 extern "C" int mf_clip_grad_norm(const void* g16, const float* g32, const void* chunks, int nchunks, float max_norm,
                                  float* part, float* out, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (nchunks <= 0) return 0;
-  sumsq_chunks_kernel<<<nchunks, 256, 0, st>>>((const f16*)g16, g32, (const Chunk*)chunks, part);
-  MF_CHECK_LAUNCH();
-  clip_coef_kernel<<<1, 1024, 0, st>>>(part, (const Chunk*)chunks, nchunks, max_norm, out);
-  MF_CHECK_LAUNCH();
-  return 0;
+  return clip_launches(g16, g32, chunks, nchunks, max_norm, part, out, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// The whole optimizer step in three launches: clip_grad_norm_ (partial sums, then the coefficient, which also
-// latches hyper[4] = max(hyper[4], *halt_src, *input_flag) -- the two torch.maximum launches the engine used to
-// make, at the step's start for the input check and here for the loss), then SGD over the fp16 and the fp32 flat
-// buffers in one launch.  Bit-identical to mf_clip_grad_norm + two mf_sgd_step.  input_flag may be null.
 extern "C" int mf_sgd_step(void* p, void* g, void* buf, int64_t n, int is16, const float* coef, const float* hyper,
-                           void* stream);
-extern "C" int mf_optimizer_step(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
-                                 int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
-                                 float* hyper, const float* halt_src, const int* input_flag, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (nchunks > 0) {
-    sumsq_chunks_kernel<<<nchunks, 256, 0, st>>>((const f16*)g16, g32, (const Chunk*)chunks, part);
-    MF_CHECK_LAUNCH();
-  }
-  clip_coef_kernel<<<1, 1024, 0, st>>>(part, (const Chunk*)chunks, nchunks, max_norm, out, hyper, halt_src,
-                                       input_flag);
-  MF_CHECK_LAUNCH();
-  const bool vec16 = n16 % 8 == 0 && (uintptr_t)p16 % 32 == 0 && (uintptr_t)g16 % 32 == 0 && (uintptr_t)b16 % 32 == 0;
-  const bool vec32 = n32 % 8 == 0 && (uintptr_t)p32 % 32 == 0 && (uintptr_t)g32 % 32 == 0 && (uintptr_t)b32 % 32 == 0;
-  if (vec16 && vec32 && n16 + n32 > 0) {
-    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
-    sgd8_both_kernel<<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, n16 / 8, p32, g32, b32, n32 / 8,
-                                                  nb16, out, hyper);
-    MF_CHECK_LAUNCH();
-    return 0;
-  }
-  int rc = mf_sgd_step(p16, g16, b16, n16, 1, out, hyper, stream);
-  return rc ? rc : mf_sgd_step(p32, g32, b32, n32, 0, out, hyper, stream);
-}
-
-extern "C" int mf_sgd_step(void* p, void* g, void* buf, int64_t n, int is16, const float* coef,
-                           const float* hyper, void* stream) {
-  if (n <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec = n % 8 == 0 && (uintptr_t)p % 32 == 0 && (uintptr_t)g % 32 == 0 && (uintptr_t)buf % 32 == 0;
-  if (vec && is16)
-    sgd8_kernel<f16><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, n / 8, coef, hyper);
-  else if (vec)
-    sgd8_kernel<float><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, n / 8, coef, hyper);
-  else if (is16)
-    sgd_kernel<f16><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, n, coef, hyper);
-  else
-    sgd_kernel<float><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, n, coef, hyper);
-  MF_CHECK_LAUNCH();
-  return 0;
+                           void* stream) {
+  return sgd_step<false>(p, g, buf, nullptr, n, is16, coef, hyper, (hipStream_t)stream);
 }
 
 // mf_sgd_step with the FedProx term mu * (p - pglob), mu = hyper[5] (a 6-float hyper)
@@ -667,88 +594,53 @@ extern "C" int mf_sgd_prox_step(void* p, void* g, void* buf, const void* pglob, 
                                 const float* hyper, void* stream) {
   if (n <= 0) return 0;
   if (!pglob) return mf_set_error("mf_sgd_prox_step: no global copy", -1);
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec = n % 8 == 0 && (uintptr_t)p % 32 == 0 && (uintptr_t)g % 32 == 0 && (uintptr_t)buf % 32 == 0 &&
-                   (uintptr_t)pglob % 32 == 0;
-  if (vec && is16)
-    sgd8_prox_kernel<f16><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n / 8, coef,
-                                                       hyper);
-  else if (vec)
-    sgd8_prox_kernel<float><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob,
-                                                         n / 8, coef, hyper);
-  else if (is16)
-    sgd_prox_kernel<f16><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n, coef, hyper);
-  else
-    sgd_prox_kernel<float><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, n, coef,
-                                                    hyper);
-  MF_CHECK_LAUNCH();
-  return 0;
+  return sgd_step<true>(p, g, buf, pglob, n, is16, coef, hyper, (hipStream_t)stream);
 }
 
-// mf_optimizer_step with the proximal SGD launch: the partial sums and the coefficient launch are the same kernels
-// (the clip norm is the model gradient's, without the proximal term)
+extern "C" int mf_optimizer_step(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
+                                 int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
+                                 float* hyper, const float* halt_src, const int* input_flag, void* stream) {
+  return optimizer_step<false>(p16, g16, b16, nullptr, n16, p32, g32, b32, nullptr, n32, chunks, nchunks, max_norm,
+                               part, out, hyper, halt_src, input_flag, (hipStream_t)stream);
+}
+
+// mf_optimizer_step with the proximal SGD launch
 extern "C" int mf_optimizer_step_prox(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
                                       int64_t n32, const void* chunks, int nchunks, float max_norm, float* part,
                                       float* out, float* hyper, const float* halt_src, const int* input_flag,
                                       const void* glob16, const float* glob32, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if ((n16 > 0 && !glob16) || (n32 > 0 && !glob32)) return mf_set_error("mf_optimizer_step_prox: no global copy", -1);
-  if (nchunks > 0) {
-    sumsq_chunks_kernel<<<nchunks, 256, 0, st>>>((const f16*)g16, g32, (const Chunk*)chunks, part);
-    MF_CHECK_LAUNCH();
-  }
-  clip_coef_kernel<<<1, 1024, 0, st>>>(part, (const Chunk*)chunks, nchunks, max_norm, out, hyper, halt_src,
-                                       input_flag);
+  return optimizer_step<true>(p16, g16, b16, glob16, n16, p32, g32, b32, glob32, n32, chunks, nchunks, max_norm, part,
+                              out, hyper, halt_src, input_flag, (hipStream_t)stream);
+}
+
+extern "C" int mf_fedavg_pack(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
+                              float* bucket, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack: negative size", -1);
+  pack_kernel<false><<<nblk(n16 + n32 + TAIL<false>), 256, 0, (hipStream_t)stream>>>((const f16*)p16, n16, p32, n32,
+                                                                                     invalid_flag, bucket, 1.f);
   MF_CHECK_LAUNCH();
-  const bool vec16 = n16 % 8 == 0 && (uintptr_t)p16 % 32 == 0 && (uintptr_t)g16 % 32 == 0 &&
-                     (uintptr_t)b16 % 32 == 0 && (uintptr_t)glob16 % 32 == 0;
-  const bool vec32 = n32 % 8 == 0 && (uintptr_t)p32 % 32 == 0 && (uintptr_t)g32 % 32 == 0 &&
-                     (uintptr_t)b32 % 32 == 0 && (uintptr_t)glob32 % 32 == 0;
-  if (vec16 && vec32 && n16 + n32 > 0) {
-    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
-    sgd8_prox_both_kernel<<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, (const f16*)glob16, n16 / 8,
-                                                       p32, g32, b32, glob32, n32 / 8, nb16, out, hyper);
-    MF_CHECK_LAUNCH();
-    return 0;
-  }
-  int rc = mf_sgd_prox_step(p16, g16, b16, glob16, n16, 1, out, hyper, stream);
-  return rc ? rc : mf_sgd_prox_step(p32, g32, b32, glob32, n32, 0, out, hyper, stream);
+  return 0;
 }
 
 extern "C" int mf_fedavg_pack_weighted(const void* p16, int64_t n16, const float* p32, int64_t n32,
                                        const int* invalid_flag, float weight, float* bucket, void* stream) {
   if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack_weighted: negative size", -1);
   if (!(weight > 0.f) || __builtin_isinf(weight)) return mf_set_error("mf_fedavg_pack_weighted: weight not in (0, inf)", -1);
-  pack_weighted_kernel<<<nblk(n16 + n32 + 2), 256, 0, (hipStream_t)stream>>>((const f16*)p16, n16, p32, n32,
-                                                                             invalid_flag, weight, bucket);
-  MF_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int mf_fedavg_unpack_weighted(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32,
-                                         void* g16, float* g32, void* stream) {
-  if (n16 + n32 <= 0) return 0;
-  unpack_weighted_kernel<<<nblk(n16 + n32), 256, 0, (hipStream_t)stream>>>(bucket, (f16*)p16, n16, p32, n32, (f16*)g16,
-                                                                           g32);
-  MF_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int mf_fedavg_pack(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
-                              float* bucket, void* stream) {
-  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack: negative size", -1);
-  pack_kernel<<<nblk(n16 + n32 + 1), 256, 0, (hipStream_t)stream>>>((const f16*)p16, n16, p32, n32, invalid_flag,
-                                                                    bucket);
+  pack_kernel<true><<<nblk(n16 + n32 + TAIL<true>), 256, 0, (hipStream_t)stream>>>((const f16*)p16, n16, p32, n32,
+                                                                                   invalid_flag, bucket, weight);
   MF_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int mf_fedavg_unpack(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32, void* g16,
                                 float* g32, void* stream) {
-  if (n16 + n32 <= 0) return 0;
-  unpack_kernel<<<nblk(n16 + n32), 256, 0, (hipStream_t)stream>>>(bucket, (f16*)p16, n16, p32, n32, (f16*)g16, g32);
-  MF_CHECK_LAUNCH();
-  return 0;
+  return fedavg_unpack<false>(bucket, p16, n16, p32, n32, g16, g32, stream);
+}
+
+extern "C" int mf_fedavg_unpack_weighted(const float* bucket, void* p16, int64_t n16, float* p32, int64_t n32,
+                                         void* g16, float* g32, void* stream) {
+  return fedavg_unpack<true>(bucket, p16, n16, p32, n32, g16, g32, stream);
 }
 
 // The FedOpt server step on the summed bucket (weighted = 0: [sum | votes], 1: [sum | wsum | votes]), one launch
@@ -770,9 +662,9 @@ extern "C" int mf_fedopt_step(const float* bucket, int weighted, int opt, float 
     return mf_set_error("mf_fedopt_step: null bucket, weights or global copy", -1);
   hipStream_t st = (hipStream_t)stream;
   const FedOptHyper h{opt, beta1, beta2, tau, eta};
-  auto al = [](const void* p, uintptr_t a) { return (uintptr_t)p % a == 0; };
-  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && al(bucket, 32) && al(x, 32) && al(m, 32) &&
-                   (!adaptive || al(v, 32)) && al(p16, 16) && al(g16, 16) && al(p32, 32) && al(g32, 32);
+  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && aligned(bucket, 32) && aligned(x, 32) && aligned(m, 32) &&
+                   (!adaptive || aligned(v, 32)) && aligned(p16, 16) && aligned(g16, 16) && aligned(p32, 32) &&
+                   aligned(g32, 32);
   if (vec) {
     const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
     fedopt8_step_kernel<<<nb16 + nb32, 256, 0, st>>>(bucket, weighted, h, x, m, adaptive ? v : nullptr, (f16*)p16, n16,
@@ -793,8 +685,8 @@ extern "C" int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* 
   if ((n16 > 0 && (!p16 || !g16)) || (n32 > 0 && (!p32 || !g32)))
     return mf_set_error("mf_fedopt_deliver: null weights or global copy", -1);
   hipStream_t st = (hipStream_t)stream;
-  auto al = [](const void* p, uintptr_t a) { return (uintptr_t)p % a == 0; };
-  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && al(x, 32) && al(p16, 16) && al(g16, 16) && al(p32, 32) && al(g32, 32);
+  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && aligned(x, 32) && aligned(p16, 16) && aligned(g16, 16) &&
+                   aligned(p32, 32) && aligned(g32, 32);
   if (vec) {
     const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
     fedopt8_deliver_kernel<<<nb16 + nb32, 256, 0, st>>>(x, (f16*)p16, n16, p32, n32, (f16*)g16, g32, nb16);

@@ -606,23 +606,35 @@ def clip_grad_norm(g16, g32, chunks, nchunks, max_norm, part, out):
     _rec(ev)
 
 
-def sgd_step(p, g, buf, coef, hyper):
-    """hyper: device fp32 tensor {lr, momentum, weight_decay, first_step}."""
-    # p, g, momentum read; p, momentum written (each at the parameter's element size)
-    ev = _hbm(f"sgd_step/{'f16' if p.dtype == torch.float16 else 'f32'}", p.numel() * 5.0 * p.element_size())
-    call("mf_sgd_step", _p(p), _p(g), _p(buf), p.numel(), int(p.dtype == torch.float16), _p(coef), _p(hyper), _s())
+def _sgd_call(name, p, g, buf, coef, hyper, *pglob):
+    # p, g, momentum read; p, momentum written (each at the parameter's element size); sgd_prox_step also reads pglob
+    is16 = p.dtype == torch.float16
+    ev = _hbm(f"{name}/{'f16' if is16 else 'f32'}", p.numel() * (5.0 + len(pglob)) * p.element_size())
+    call("mf_" + name, _p(p), _p(g), _p(buf), *map(_p, pglob), p.numel(), int(is16), _p(coef), _p(hyper), _s())
     _rec(ev)
+
+
+def _optimizer_call(name, p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
+                    input_flag, *glob):
+    # every gradient read twice; p, g, momentum read and written: 5 streams per element, 6 with the two global copies
+    nb = g16.numel() * 2.0 + g32.numel() * 4.0 + (p16.numel() * 2.0 + p32.numel() * 4.0) * (5.0 + len(glob) / 2)
+    ev = _hbm(name, nb)
+    call("mf_" + name, _p(p16), _p(g16), _p(b16), p16.numel(), _p(p32), _p(g32), _p(b32), p32.numel(), _p(chunks),
+         nchunks, float(max_norm), _p(part), _p(out), _p(hyper), _p(halt_src), _p(input_flag), *map(_p, glob), _s())
+    _rec(ev)
+
+
+def sgd_step(p, g, buf, coef, hyper):
+    """hyper: device fp32 tensor {lr, momentum, weight_decay, first_step, halt}."""
+    _sgd_call("sgd_step", p, g, buf, coef, hyper)
 
 
 def optimizer_step(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
                    input_flag=None):
     """clip_grad_norm + sgd_step(fp16) + sgd_step(fp32), with hyper[4] = max(hyper[4], halt_src[0], input_flag[0])
     folded in: three launches, bit-identical (mf_optimizer_step)."""
-    nb = g16.numel() * 2.0 + g32.numel() * 4.0 + p16.numel() * 10.0 + p32.numel() * 20.0
-    ev = _hbm("optimizer_step", nb)  # every gradient read twice; p, g, momentum read and written
-    call("mf_optimizer_step", _p(p16), _p(g16), _p(b16), p16.numel(), _p(p32), _p(g32), _p(b32), p32.numel(), _p(chunks),
-         nchunks, float(max_norm), _p(part), _p(out), _p(hyper), _p(halt_src), _p(input_flag), _s())
-    _rec(ev)
+    _optimizer_call("optimizer_step", p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper,
+                    halt_src, input_flag)
 
 
 def _check_flat(name, t, dtype, numel=None):
@@ -650,11 +662,7 @@ def sgd_prox_step(p, g, buf, pglob, coef, hyper):
     if p.numel() and pglob.data_ptr() == p.data_ptr():
         raise ValueError("pglob: a buffer of its own required (it is p)")
     _check_prox_hyper(hyper)
-    # sgd_step's streams plus one read of the global copy
-    ev = _hbm(f"sgd_prox_step/{'f16' if p.dtype == torch.float16 else 'f32'}", p.numel() * 6.0 * p.element_size())
-    call("mf_sgd_prox_step", _p(p), _p(g), _p(buf), _p(pglob), p.numel(), int(p.dtype == torch.float16), _p(coef),
-         _p(hyper), _s())
-    _rec(ev)
+    _sgd_call("sgd_prox_step", p, g, buf, coef, hyper, pglob)
 
 
 def optimizer_step_prox(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
@@ -671,12 +679,8 @@ def optimizer_step_prox(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm,
     if (p16.numel() and glob16.data_ptr() == p16.data_ptr()) or (p32.numel() and glob32.data_ptr() == p32.data_ptr()):
         raise ValueError("glob16 / glob32: buffers of their own required")
     _check_prox_hyper(hyper)
-    nb = g16.numel() * 2.0 + g32.numel() * 4.0 + p16.numel() * 12.0 + p32.numel() * 24.0
-    ev = _hbm("optimizer_step_prox", nb)  # optimizer_step's bytes plus one read of the global copies
-    call("mf_optimizer_step_prox", _p(p16), _p(g16), _p(b16), p16.numel(), _p(p32), _p(g32), _p(b32), p32.numel(),
-         _p(chunks), nchunks, float(max_norm), _p(part), _p(out), _p(hyper), _p(halt_src), _p(input_flag),
-         _p(glob16), _p(glob32), _s())
-    _rec(ev)
+    _optimizer_call("optimizer_step_prox", p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper,
+                    halt_src, input_flag, glob16, glob32)
 
 
 def fedavg_pack_weighted(p16, p32, invalid_flag, weight, bucket):

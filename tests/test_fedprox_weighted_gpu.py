@@ -91,6 +91,59 @@ def test_pack_and_unpack_weighted_kernels(dev):
         ops.fedavg_pack_weighted(d16.float(), d32, flag, 3.0, bucket)
 
 
+def test_plain_and_unit_weight_chains_agree(dev):
+    """The plain and the weighted pack / unpack kernels are two instantiations of one body: with every weight 1.0
+    (1.0f * x is exact; the summed weights and the vote count are both 3.0f) pack x 3 -> reduce_ordered -> unpack
+    gives the plain chain's p16, p32, g16, g32 bit for bit, and the plain chain equals torch's
+    acc = x0; acc += x1; acc += x2; (acc / 3).half().  Ragged n16 = 37, n32 = 4099: the n16 split sits mid-block."""
+    clients = [_client(c) for c in range(3)]
+    n16, n32 = clients[0][0].numel(), clients[0][1].numel()
+    n = n16 + n32
+    dclients = [(p16.to(dev), p32.to(dev)) for p16, p32 in clients]
+    prev16 = torch.full((n16,), 0.5, dtype=torch.float16, device=dev)
+    prev32 = torch.full((n32,), 0.25, device=dev)
+
+    def chain(weighted, invalid):
+        tail = 2 if weighted else 1
+        gathered = torch.empty(3, n + tail, device=dev)
+        for c, (p16, p32) in enumerate(dclients):
+            flag = torch.full((1,), int(c in invalid), dtype=torch.int32, device=dev)
+            if weighted:
+                ops.fedavg_pack_weighted(p16, p32, flag, 1.0, gathered[c])
+            else:
+                ops.fedavg_pack(p16, p32, flag, gathered[c])
+        total = torch.empty(n + tail, device=dev)
+        ops.fedavg_reduce_ordered(gathered.view(-1), 3, total)
+        assert all(t.item() == 3.0 - len(invalid) for t in total[n:])
+        o16, o32 = torch.full_like(prev16, 5.0), torch.full_like(prev32, 5.0)
+        g16, g32 = prev16.clone(), prev32.clone()
+        (ops.fedavg_unpack_weighted if weighted else ops.fedavg_unpack)(total, o16, o32, g16, g32)
+        return o16, o32, g16, g32
+
+    def host_mean(which):
+        xs = [torch.cat([clients[c][0].float(), clients[c][1]]) for c in which]
+        acc = xs[0].clone()
+        for x in xs[1:]:
+            acc += x
+        v = (acc / len(which)).half()
+        return v[:n16], v[n16:].float()
+
+    for invalid, which in (((), (0, 1, 2)), ((1,), (0, 2))):
+        plain, weighted = chain(False, invalid), chain(True, invalid)
+        ref16, ref32 = host_mean(which)
+        assert torch.equal(plain[0].cpu(), ref16) and torch.equal(plain[1].cpu(), ref32)
+        assert torch.equal(plain[2], plain[0]) and torch.equal(plain[3], plain[1])  # kept as the global copy
+        for a, b in zip(plain, weighted):
+            assert torch.equal(a, b)
+    # the invalid client changed the mean
+    assert not torch.equal(host_mean((0, 1, 2))[1], host_mean((0, 2))[1])
+    # all three invalid: both chains restore the previous global copy, which stays
+    for weighted in (False, True):
+        o16, o32, g16, g32 = chain(weighted, (0, 1, 2))
+        assert torch.equal(o16, prev16) and torch.equal(o32, prev32)
+        assert torch.equal(g16, prev16) and torch.equal(g32, prev32)
+
+
 def test_weighted_pack_reduce_unpack_chain_is_bit_exact(dev):
     clients = [_client(c) for c in range(3)]
     weights = (3.0, 1.0, 2.0)
