@@ -97,16 +97,17 @@ __global__ void text_assemble_kernel(const f16* __restrict__ prefix, const f16* 
 }
 
 // ---------------------------------------------------------------- deep prompt inject
-// x[n*L + row0 + r, :] = fp16(prompt[r, :])  (prompt fp32, the `.half()` at clip/model.py:327,344)
-__global__ void inject_kernel(f16* __restrict__ x, const float* __restrict__ prompt, int N, int L, int row0,
-                              int nrows, int D) {
+// x[n*L + row0 + r, :] = fp16(prompt[r, :])  (prompt fp32, the `.half()` at clip/model.py:327,344); ldx: x's row
+// stride in elements
+__global__ void inject_kernel(f16* __restrict__ x, int64_t ldx, const float* __restrict__ prompt, int N, int L,
+                              int row0, int nrows, int D) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = N * nrows * D;
   if (t >= total) return;
   const int d = t % D;
   const int r = (t / D) % nrows;
   const int n = t / (D * nrows);
-  x[((int64_t)n * L + row0 + r) * D + d] = (f16)prompt[r * D + d];
+  x[((int64_t)n * L + row0 + r) * ldx + d] = (f16)prompt[r * D + d];
 }
 
 // out[r, d] (=|+=) sum_n dx[n*L + row0 + r, d]  (fp32 accumulation in a fixed order), then the
@@ -535,13 +536,22 @@ extern "C" int mf_text_assemble(const void* prefix, const void* ctx, const void*
   return 0;
 }
 
-extern "C" int mf_prompt_inject_fwd(void* x, const float* prompt, int N, int L, int row0, int nrows, int D,
-                                    void* stream) {
+// mf_prompt_inject_fwd on rows ldx >= D elements apart: mf_layernorm_fwd_inject's two-kernel path (layernorm.hip),
+// not part of the C ABI of include/mapfed.h
+extern "C" int mf_prompt_inject_fwd_ld(void* x, int64_t ldx, const float* prompt, int N, int L, int row0, int nrows,
+                                       int D, void* stream) {
   if (N <= 0) return 0;
   if (row0 < 0 || row0 + nrows > L) return mf_set_error("mf_prompt_inject_fwd: rows out of range", -1);
-  inject_kernel<<<nblk((int64_t)N * nrows * D), 256, 0, (hipStream_t)stream>>>((f16*)x, prompt, N, L, row0, nrows, D);
+  if (ldx < D) return mf_set_error("mf_prompt_inject_fwd: ldx < D", -1);
+  inject_kernel<<<nblk((int64_t)N * nrows * D), 256, 0, (hipStream_t)stream>>>((f16*)x, ldx, prompt, N, L, row0,
+                                                                               nrows, D);
   MF_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int mf_prompt_inject_fwd(void* x, const float* prompt, int N, int L, int row0, int nrows, int D,
+                                    void* stream) {
+  return mf_prompt_inject_fwd_ld(x, D, prompt, N, L, row0, nrows, D, stream);
 }
 
 extern "C" int mf_prompt_inject_bwd(void* dx, int N, int L, int row0, int nrows, int D, void* out, int out_f16,

@@ -422,7 +422,8 @@ __global__ __launch_bounds__(HWB * 32) void ln_bwd2_kernel(const f16* __restrict
 // one row per half-wave (16 half-waves per row block) when the row blocks alone cannot fill the chip: below 256
 // blocks (the c4 text tower's 183, the small clients' ~50; tests/diagnostics/ln_bench.py, r04: 8.43 -> 7.58 us at
 // 2 926 x 512, 8.11 -> 7.43 at 796 x 768; at 6 368 x 768, 398 blocks, 14.3 -> 15.7, so not there).  Both forms
-// produce bit-identical partials (measured r04); tests/test_kernels_gpu.py::test_layernorm covers both regimes.
+// produce bit-identical partials (tests/test_reduction_kernels_gpu.py compares them at 255 and 256 blocks);
+// tests/test_kernels_gpu.py::test_layernorm covers both regimes.
 inline bool ln_bwd_wide(int nblk) { return nblk < 256; }
 
 }  // namespace
@@ -542,12 +543,13 @@ extern "C" int mf_col_reduce_batch(const void* descs, int n, int max_cols, void*
   return 0;
 }
 
-extern "C" int mf_prompt_inject_fwd(void* x, const float* prompt, int N, int L, int row0, int nrows, int D,
-                                    void* stream);
+extern "C" int mf_prompt_inject_fwd_ld(void* x, int64_t ldx, const float* prompt, int N, int L, int row0, int nrows,
+                                       int D, void* stream);
 
 // LayerNorm with the deep-prompt injection of the same rows fused in: equivalent (bit for bit) to
 // mf_prompt_inject_fwd(x, prompt, rows / L, L, row0, nrows, D) followed by mf_layernorm_fwd on x
-// (clip/model.py:320-349 injection at the start of a block, then its ln_1).
+// (clip/model.py:320-349 injection at the start of a block, then its ln_1).  Rows that are not contiguous
+// (ldx != D) or not 16-byte aligned take those two kernels, the injection at row stride ldx.
 extern "C" int mf_layernorm_fwd_inject(void* x, int64_t ldx, const float* gamma, const float* beta, void* y,
                                        int64_t ldy, float* mean, float* rstd, int rows, int D, const float* prompt,
                                        int L, int row0, int nrows, void* stream) {
@@ -556,7 +558,7 @@ extern "C" int mf_layernorm_fwd_inject(void* x, int64_t ldx, const float* gamma,
   hipStream_t st = (hipStream_t)stream;
   const bool v16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && (ldx % 8 == 0) && (ldy % 8 == 0);
   if (ldx != D || !(v16 && (D == 768 || D == 512))) {
-    const int rc = mf_prompt_inject_fwd(x, prompt, rows / L, L, row0, nrows, D, stream);
+    const int rc = mf_prompt_inject_fwd_ld(x, ldx, prompt, rows / L, L, row0, nrows, D, stream);
     return rc ? rc : mf_layernorm_fwd(x, ldx, nullptr, gamma, beta, y, ldy, mean, rstd, rows, D, stream);
   }
   const dim3 g2((rows + 7) / 8);
