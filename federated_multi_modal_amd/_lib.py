@@ -26,6 +26,7 @@ SIGNATURES = {
     "mf_attention_fwd": [P, L, P, L, P, I, I, I, I, I, P],
     "mf_attention_fwd_rows": [P, L, P, L, P, I, I, I, I, I, I, P],
     "mf_attention_bwd": [P, L, P, L, P, L, P, P, I, P, L, I, I, I, I, P],
+    "mf_attention_bwd_rows": [P, L, P, L, P, L, P, I, P, L, I, I, I, I, I, P],
     "mf_qkv_attention_fwd": [P, L, I, P, P, P, L, P, L, P, I, I, I, I, I, P],
     "mf_qkv_attention_supported": [I, I, I, I],
     "mf_im2col_patch": [P, I, P, I, I, I, P],
@@ -96,6 +97,11 @@ def lib():
     if not os.path.exists(path):
         raise MapfedError(f"libmapfed.so not found at {path}: run __graft_entry__.build() "
                           "(make -C federated_multi_modal_amd/csrc)")
+    # torch first: it loads its own copy of the HIP runtime by path, and the library must bind to that one.  Loaded
+    # before torch, the library brings in the system's copy, the process ends up with two runtimes, and the second
+    # one to initialise finds no device (every kernel call fails with hipErrorNoDevice) -- the order build() followed
+    # by smoke() in one process runs in.
+    import torch  # noqa: F401
     h = ctypes.CDLL(path)
     h.mf_last_error.restype = ctypes.c_char_p
     h.mf_last_error.argtypes = []

@@ -66,6 +66,29 @@ MF_DEV void stage_rows(f16* img, const f16* base, int64_t ld, int L, int col0) {
                                      (lds_ptr_t)(img + i * 8 * 64), 16, 0, 0);
   }
 }
+// The ROWS variant of attn_bwd_fused_kernel: the first ng 8-row groups only.  stage_rows_n is stage_rows cut short;
+// stage_rows_live goes through registers so that rows >= live are zeros in LDS and are never read from memory
+// (same swizzled image: slot lane of group i holds source chunk (lane & 7) ^ (row & 7) of row 8 i + lane / 8).
+MF_DEV void stage_rows_n(f16* img, const f16* base, int64_t ld, int L, int col0, int ng) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
+  for (int i = w; i < ng; i += nw) {
+    int row = i * 8 + lrow;
+    row = row < L ? row : L - 1;
+    __builtin_amdgcn_global_load_lds((const void*)(base + (int64_t)row * ld + col0 + lchunk * 8),
+                                     (lds_ptr_t)(img + i * 8 * 64), 16, 0, 0);
+  }
+}
+MF_DEV void stage_rows_live(f16* img, const f16* base, int64_t ld, int live, int col0, int ng) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
+  for (int i = w; i < ng; i += nw) {
+    const int row = i * 8 + lrow;
+    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (row < live) v = *(const f16x8*)(base + (int64_t)row * ld + col0 + lchunk * 8);
+    *(f16x8*)(img + i * 8 * 64 + lane * 8) = v;
+  }
+}
 MF_DEV void stage_wait() {
   __builtin_amdgcn_s_waitcnt((0 & 15) | (7 << 4) | (15 << 8));  // vmcnt(0): this wave's LDS-DMA landed
   __syncthreads();                                              // ... and every other wave's
@@ -795,12 +818,18 @@ MF_DEV f16x4 tr_read_p(const f16* img, int pitch, int r0, int c0, int lane) {
   return __builtin_bit_cast(f16x4, v);
 }
 
-template <int LP, bool CAUSAL, int KT>
+// attn_bwd_fused_kernel, the schedule above.  ROWS (mf_attention_bwd_rows): dO is zero at query rows >= q_rows.  Those rows of dout / out / lse are not read
+// (dO staged as zeros, D = 0, LSE = +inf, so P = dS = 0 there as for padded queries); phase 1 sweeps only the
+// query blocks below ceil(q_rows / 32) -- the others would add exact zeros to dK / dV -- and phase 2 computes
+// dQ for the 16-query tiles below q_rows and stores +0 (what dS = 0 gives) for the other queries.
+template <int LP, bool CAUSAL, int KT, bool ROWS = false>
 __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
     const f16* __restrict__ qkv, int64_t ld_qkv, const f16* __restrict__ out, int64_t ld_out,
     const f16* __restrict__ dout, int64_t ld_dout, const float* __restrict__ lse, int ld_lse,
-    f16* __restrict__ dqkv, int64_t ld_dqkv, int L, int H) {
+    f16* __restrict__ dqkv, int64_t ld_dqkv, int L, int H, int q_rows) {
   constexpr int PT = BwdLds<LP>::P;
+  const int live = ROWS ? q_rows : L;                 // queries whose dO / O / LSE are read
+  const int nqb = ROWS ? (q_rows + 31) / 32 : LP / 32;  // 32-query blocks phase 1 sweeps
   __shared__ __attribute__((aligned(16))) f16 smem[BwdLds<LP>::ELEMS];
   f16* sQ = smem;                     // [LP][64] swizzled (phase 2: K)
   f16* sdO = smem + LP * 64;          // [LP][64] swizzled
@@ -814,8 +843,13 @@ __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
   const f16* obase = out + (int64_t)n * L * ld_out;
   const f16* dobase = dout + (int64_t)n * L * ld_dout;
   MF_ASTAMP(0);
-  stage_rows<LP>(sQ, base, ld_qkv, L, h * 64);
-  stage_rows<LP>(sdO, dobase, ld_dout, L, h * 64);
+  if (ROWS) {
+    stage_rows_n(sQ, base, ld_qkv, L, h * 64, 4 * nqb);
+    stage_rows_live(sdO, dobase, ld_dout, live, h * 64, 4 * nqb);
+  } else {
+    stage_rows<LP>(sQ, base, ld_qkv, L, h * 64);
+    stage_rows<LP>(sdO, dobase, ld_dout, L, h * 64);
+  }
 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -827,7 +861,7 @@ __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
     const int q = 16 * KT * w + lane / LPQ;
     const int part = lane % LPQ;
     float d = 0.f;
-    if (q < L) {
+    if (q < live) {
       const f16* o = obase + (int64_t)q * ld_out + h * 64 + DPL * part;
       const f16* g = dobase + (int64_t)q * ld_dout + h * 64 + DPL * part;
 #pragma unroll
@@ -840,9 +874,9 @@ __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
 #pragma unroll
     for (int o2 = 1; o2 < LPQ; o2 <<= 1) d += __shfl_xor(d, o2, 64);
     if (part == 0) {
-      sD[q] = q < L ? d : 0.f;
+      sD[q] = q < live ? d : 0.f;
       // LSE in base 2 (P = exp2(S * scale * log2e - LSE * log2e)); +inf masks padded queries
-      sL[q] = q < L ? lse[(int64_t)nh * ld_lse + q] * 1.4426950408889634f : INFINITY;
+      sL[q] = q < live ? lse[(int64_t)nh * ld_lse + q] * 1.4426950408889634f : INFINITY;
     }
   }
   // the wave's keys: K and V fragments straight to registers
@@ -868,7 +902,7 @@ __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dv[kt][dt] = dk[kt][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
-  for (int qp = 0; qp < LP / 32; ++qp) {
+  for (int qp = 0; qp < nqb; ++qp) {
     if (CAUSAL && 32 * qp + 31 < k0) continue;  // (KT = 1 waves: k0 may sit mid-block)  // every query of the block precedes every key of the wave
     f16x8 pf[KT], dsf[KT];
 #pragma unroll
@@ -960,6 +994,7 @@ __global__ __launch_bounds__(64 * (LP / (16 * KT))) void attn_bwd_fused_kernel(
     for (int dt = 0; dt < 4; ++dt) dq[qt][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int ks = 0; ks < LP / 32; ++ks) {
+    if (ROWS && q0 >= q_rows) break;  // no live query in the wave's tiles: dQ = +0
     if (CAUSAL && 32 * ks > q0 + 16 * KT - 1) break;
     f16x8 dsf[KT];
 #pragma unroll
@@ -1196,11 +1231,11 @@ extern "C" int mf_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out
   if (causal)                                                                                                      \
     attn_bwd_fused_kernel<P, true, 1><<<gridf, blockf, 0, st>>>((const f16*)qkv, ld_qkv, (const f16*)out, ld_out,  \
                                                               (const f16*)dout, ld_dout, lse, ld_lse, (f16*)dqkv,   \
-                                                              ld_dqkv, L, H);                                      \
+                                                              ld_dqkv, L, H, L);                                   \
   else                                                                                                             \
     attn_bwd_fused_kernel<P, false, 1><<<gridf, blockf, 0, st>>>((const f16*)qkv, ld_qkv, (const f16*)out, ld_out, \
                                                                (const f16*)dout, ld_dout, lse, ld_lse, (f16*)dqkv,  \
-                                                               ld_dqkv, L, H);
+                                                               ld_dqkv, L, H, L);
     switch (LP) {
       case 32: CALLBF(32); break;
       case 64: CALLBF(64); break;
@@ -1234,6 +1269,43 @@ extern "C" int mf_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out
   }
   MF_ATTN_DISPATCH(LP, CALLB)
 #undef CALLB
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// mf_attention_bwd for a gradient that is zero at query rows >= q_rows of every sequence (the training step's last
+// vision block: ln_post reads the class token only, so dO has one live row per image).  Rows >= q_rows of dout, out
+// and lse are not read (they may hold anything); qkv is read at every row.  dqkv is written in full and is bit for
+// bit what mf_attention_bwd gives for a dout with exact zeros in those rows.  Non-causal sequences of up to 224 rows
+// (the fused kernel) only: anything else is an error, not a detour through the full path, which would read the rows
+// this entry promises not to.
+extern "C" int mf_attention_bwd_rows(const void* qkv, int64_t ld_qkv, const void* out, int64_t ld_out,
+                                     const void* dout, int64_t ld_dout, const float* lse, int ld_lse, void* dqkv,
+                                     int64_t ld_dqkv, int N, int L, int H, int causal, int q_rows, void* stream) {
+  if (N <= 0) return 0;
+  if (L <= 0 || L > 224) return mf_set_error("mf_attention_bwd_rows: 0 < L <= 224 required", -1);
+  if (causal) return mf_set_error("mf_attention_bwd_rows: causal masks are not supported", -1);
+  if (q_rows <= 0 || q_rows > L) return mf_set_error("mf_attention_bwd_rows: 0 < q_rows <= L required", -1);
+  if (ld_lse < L || (ld_qkv % 8) || (ld_out % 8) || (ld_dout % 8) || (ld_dqkv % 4))
+    return mf_set_error("mf_attention_bwd_rows: bad strides", -1);
+  const int LP = padded_len(L);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 gridf(N * H), blockf(64 * (LP / 16));
+#define CALLBR(P)                                                                                                     \
+  attn_bwd_fused_kernel<P, false, 1, true><<<gridf, blockf, 0, st>>>((const f16*)qkv, ld_qkv, (const f16*)out, ld_out, \
+                                                                     (const f16*)dout, ld_dout, lse, ld_lse,         \
+                                                                     (f16*)dqkv, ld_dqkv, L, H, q_rows);
+  switch (LP) {
+    case 32: CALLBR(32); break;
+    case 64: CALLBR(64); break;
+    case 96: CALLBR(96); break;
+    case 128: CALLBR(128); break;
+    case 160: CALLBR(160); break;
+    case 192: CALLBR(192); break;
+    case 224: CALLBR(224); break;
+    default: return mf_set_error("attention: bad padded length", -1);
+  }
+#undef CALLBR
   MF_CHECK_LAUNCH();
   return 0;
 }

@@ -1275,6 +1275,94 @@ int launch_tile8f(const GemmArgs& a, int epi, hipStream_t st) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// gemm_sm: products of at most 64 rows (the class-row block of the vision tower: 32 rows against N = 768 / 3072,
+// K = 768 / 3072; the head's feature projections).  On the tile kernels such a product is a dozen workgroups, each
+// a serial K loop whose every step waits for its own operand loads: latency, not work.  Here a workgroup of 8
+// waves owns a 32-row x 16-column tile (N / 16 workgroups), wave w owns K steps [w PS, (w + 1) PS) of it and loads
+// ALL its fragments straight into registers at once (the weight rows from HBM, A from L2), so the whole panel is in
+// flight together.  The accumulators then pass through the waves in K order (LDS, one barrier per wave), so every
+// output element is still one chain of v_mfma_f32_16x16x32_f16 from a zero accumulator over k ascending in 32-deep
+// steps, with the tile kernels' operand order and k-to-lane mapping, and the epilogue is epilogue_store itself:
+// bit-identical to every tile.  K <= PS * 32 * 8.
+constexpr int SM_NW = 8;
+template <int PS, int EPI>
+__global__ __launch_bounds__(SM_NW * 64) void gemm_sm_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) float s_acc[2][64][4];
+  __shared__ __attribute__((aligned(16))) f16 s_c[32 * (16 + 8)];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fg = lane >> 4;
+  const int n0 = blockIdx.x * 16, m0 = blockIdx.y * 32;
+  const int steps = g.K / 32;
+  const int s0 = wid * PS;
+  const int ns = min(PS, steps - s0);  // this wave's K steps (<= 0: none)
+  const bool two = m0 + 16 < g.M;      // the tile's second 16-row block holds rows
+  // rows past N / M re-read the last row: finite, and the epilogue stores nothing for them
+  const f16* wrow = g.B + (int64_t)min(n0 + fr, g.N - 1) * g.ldb + 8 * fg;
+  const f16* arow0 = g.A + (int64_t)min(m0 + fr, g.M - 1) * g.lda + 8 * fg;
+  const f16* arow1 = g.A + (int64_t)min(m0 + 16 + fr, g.M - 1) * g.lda + 8 * fg;
+  f16x8 wf[PS], af0[PS], af1[PS];
+#pragma unroll
+  for (int s = 0; s < PS; ++s) {
+    wf[s] = af0[s] = af1[s] = f16x8{};
+    if (s < ns) {
+      const int k = (s0 + s) * 32;
+      wf[s] = *(const f16x8*)(wrow + k);
+      af0[s] = *(const f16x8*)(arow0 + k);
+      if (two) af1[s] = *(const f16x8*)(arow1 + k);
+    }
+  }
+  const int turns = (steps + PS - 1) / PS;  // <= SM_NW (host)
+  for (int t = 0; t < turns; ++t) {
+    if (wid == t) {
+      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+      if (t > 0) {
+        a0 = *(const f32x4*)s_acc[0][lane];
+        a1 = *(const f32x4*)s_acc[1][lane];
+      }
+#pragma unroll
+      for (int s = 0; s < PS; ++s) {
+        if (s < ns) {
+          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s], af0[s], a0, 0, 0, 0);
+          if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s], af1[s], a1, 0, 0, 0);
+        }
+      }
+      *(f32x4*)s_acc[0][lane] = a0;
+      *(f32x4*)s_acc[1][lane] = a1;
+    }
+    __syncthreads();
+  }
+  // every wave takes the finished accumulators of one 16-row block (waves of the same block stage the same
+  // values) and the workgroup runs the shared epilogue
+  f32x4 fin[1][1];
+  fin[0][0] = *(const f32x4*)s_acc[wid & 1][lane];
+  epilogue_store<32, 16, SM_NW * 64, 1, 1, EPI>(g, s_c, fin, m0, n0, 16 * (wid & 1), 0, tid, fr, fg);
+}
+
+int launch_small_m(const GemmArgs& a, int epi, hipStream_t st) {
+  if (a.M > 64 || a.K > 12 * 32 * SM_NW) return mf_set_error("mf_gemm: tile 50 needs M <= 64 and K <= 3072", -2);
+  dim3 grid((a.N + 15) / 16, (a.M + 31) / 32), block(SM_NW * 64);
+#define MF_SM(E)                                                       \
+  case E:                                                              \
+    if (a.K <= 4 * 32 * SM_NW) gemm_sm_kernel<4, E><<<grid, block, 0, st>>>(a); \
+    else gemm_sm_kernel<12, E><<<grid, block, 0, st>>>(a);             \
+    break;
+  switch (epi) {
+    MF_SM(EPI_NONE)
+    MF_SM(EPI_BIAS)
+    MF_SM(EPI_BIAS_RESID)
+    MF_SM(EPI_BIAS_GELU)
+    MF_SM(EPI_DGELU)
+    MF_SM(EPI_F32)
+    MF_SM(EPI_RESID)
+    default: return mf_set_error("mf_gemm: bad epilogue", -2);
+  }
+#undef MF_SM
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_tile8(const GemmArgs& a, int epi, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
@@ -1416,7 +1504,9 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
   if (tile == -1) tile = side ? kSideTile : 0;
   if (tile == 0) {  // heuristic: fill the 256 CUs (measured: tests/diagnostics/gemm_bench.py, gemm_stamps.cpp)
     const int64_t t256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-    if (t256 >= 192 && t256 <= 256 && K >= 512)
+    if (M <= 64 && K <= 3072)
+      tile = 50;  // gemm_sm: the class-row block's products and the head projections (bit-identical to the tiles)
+    else if (t256 >= 192 && t256 <= 256 && K >= 512)
       tile = 40;  // one round of 256x256 tiles on one workgroup per CU (vision QKV: 225 tiles), gemm8s
     else if (M >= 16384 && K >= 512)  // the C5 text tower (M = 77 000): many rounds of tiles whatever the
       // shape, so the tile's own efficiency decides (gemm_bench.py ... c5): the full-line 256x256 kernel for
@@ -1449,7 +1539,7 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
     } else
       tile = t128 >= 512 ? 1 : (t128 >= 256 ? 2 : 3);
   }
-  // tile ids: the ones the heuristic picks (1, 2, 3, 10, 15, 16, 26, 31, 33, 40 = gemm8f, 41 = gemm8p), plus 11 (160x128 with a
+  // tile ids: the ones the heuristic picks (1, 2, 3, 10, 15, 16, 26, 31, 33, 40 = gemm8f, 50 = gemm_sm), plus 41 = gemm8p, 11 (160x128 with a
   // 3-stage ring), 20 (gemm8s, the [256][32]-image 256x256 kernel gemm8f replaced in r05), 21 (8-wave 256x128) and
   // 22 (the unstaggered gemm8 at 256x256) as A/B baselines (tests/diagnostics/gemm_bench.py); the sweep also covered
   // 128x192, 192x128, 128x160, 160x160, 224x128, 96x192, 64x128, 160x192, 192x192, 256x128 on 4 waves and 128x256 /
@@ -1474,6 +1564,7 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
     case 22: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8<256, 256, 2, 4>(a, epilogue, st);
     case 40: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8f(a, epilogue, st);
     case 41: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8p(a, epilogue, st);
+    case 50: return launch_small_m(a, epilogue, st);
     default: return mf_set_error("mf_gemm: bad tile id", -2);
   }
 }

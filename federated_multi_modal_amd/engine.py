@@ -281,6 +281,19 @@ class _Tower:
         # row, query 0's attention, and out-proj / ln_2 / MLP on the N class rows; each row's arithmetic is the full
         # block's (GEMM rows and attention queries are independent), so the class rows are bit-identical
         self.cls_only = False
+        # train_cls_rows (switched on by MapleEngine.enable_train_cls_rows for the vision tower of a training engine):
+        # the same for the training step.  forward_loss() runs the last block after its in-projection on the class
+        # rows only and backward() follows it: the gradient of the tower's output is zero off the class rows (dX is
+        # cleared, the ln_post backward writes those rows), so the block's dX products, its ln_2 backward and the
+        # query side of its attention backward have one live row per image.  Every dW / db operand stays a
+        # full-layout buffer whose dead rows are exact zeros (dX, cls_dF) or finite values that meet only zeros (O,
+        # cls_G, cls_H2), so each sum keeps the full block's length and order and every gradient is bit for bit the
+        # full block's.  After such a step X[layers], X1[last] and O[last] hold this step's values at the class rows
+        # only (O: rows 0..15 of each sequence); the public forward() / eval_batch() always run the full block.
+        self.train_cls_rows = False
+        self._cls_pass = False  # forward_loss() is running (read by forward())
+        self._cls_fwd = False   # the last forward() ran the class-row block (read by backward())
+        self.cls_G = self.cls_H2 = self.cls_dF = None
         if self.inference:
             if any(self.grow):
                 raise NotImplementedError("EngineConfig.inference with growing (caption) sequences")
@@ -377,6 +390,7 @@ class _Tower:
         """X[0] must be filled.  deep_prompts[j] (fp32 [n_ctx, D]) is injected before layer j+1; cap [ncap, D]
         (fp16): the caption rows a growing block appends before its prompt."""
         N, D, H = self.N, self.D, self.H
+        self._cls_fwd = self.train_cls_rows and self._cls_pass
         for i in range(self.layers):
             L, R = self.Ls[i], self.Rs[i]
             x = self.X[i]
@@ -389,6 +403,9 @@ class _Tower:
                                   self.rstd1[i])
             if self.cls_only and i == self.layers - 1:
                 self._last_block_cls_rows(i, x, h1, L)
+                continue
+            if self._cls_fwd and i == self.layers - 1:
+                self._last_block_train_cls_rows(i, x, h1, L)
                 continue
             if self.fused_qkv_attn and ops.qkv_attention_supported(N, L, H, self.causal):
                 # in-projection + attention in one launch (bit-identical to the pair below)
@@ -435,6 +452,56 @@ class _Tower:
         ops.gemm_nt(g, self.p(i, "mlp.c_proj.weight"), self.Y[i][::L], bias=self.p(i, "mlp.c_proj.bias"), aux_in=x1,
                     epilogue=ops.EPI_BIAS_RESID, tile=self.tile)
 
+    def enable_train_cls_rows(self):
+        """Allocate what train_cls_rows needs and switch it on: the last block's own G / H2 / dF in the full row
+        layout, zero-filled here and from then on written through their class-row views only, and a finite O[last]
+        (its rows past 15 of each sequence are otherwise never written before the out-projection's dW reads them)."""
+        assert not self.inference and not any(self.grow) and self.live is None and not self.causal and self.L <= 224
+        z = lambda c: torch.zeros(self.R, c, device=self.e.device, dtype=F16)
+        self.cls_G, self.cls_H2, self.cls_dF = z(4 * self.D), z(self.D), z(4 * self.D)
+        self.O[-1].zero_()
+        self.train_cls_rows = True
+
+    def _last_block_train_cls_rows(self, i: int, x: torch.Tensor, h1: torch.Tensor, L: int):
+        """Block i (the last) of the training step's forward under train_cls_rows: the whole in-projection (the
+        backward needs q, k, v of every row), then _last_block_cls_rows' sequence on the class rows, except that the
+        MLP's operands land in cls_H2 / cls_G (full layout, read by the dW products) and Fp keeps the pre-activation."""
+        N, H = self.N, self.H
+        ops.gemm_nt(h1, self.p(i, "attn.in_proj_weight"), self.QKV[i], bias=self.p(i, "attn.in_proj_bias"),
+                    epilogue=ops.EPI_BIAS, tile=self.tile)
+        ops.attention_fwd_rows(self.QKV[i], N, L, H, self.causal, 1, out=self.O[i], lse=self.LSE[i])
+        x1 = self.X1[i][::L]
+        ops.gemm_nt(self.O[i][::L], self.p(i, "attn.out_proj.weight"), x1, bias=self.p(i, "attn.out_proj.bias"),
+                    aux_in=x[::L], epilogue=ops.EPI_BIAS_RESID, tile=self.tile)
+        h2 = self.cls_H2[::L]
+        ops.layernorm_fwd(x1, self.p(i, "ln_2.weight"), self.p(i, "ln_2.bias"), h2, self.mean2[i][:N],
+                          self.rstd2[i][:N])
+        g = self.cls_G[::L]
+        ops.gemm_nt(h2, self.p(i, "mlp.c_fc.weight"), g, bias=self.p(i, "mlp.c_fc.bias"), aux_out=self.Fp[i][::L],
+                    epilogue=ops.EPI_BIAS_GELU, tile=self.tile)
+        ops.gemm_nt(g, self.p(i, "mlp.c_proj.weight"), self.Y[i][::L], bias=self.p(i, "mlp.c_proj.bias"), aux_in=x1,
+                    epilogue=ops.EPI_BIAS_RESID, tile=self.tile)
+
+    def _last_block_bwd_cls_rows(self, i: int, L: int, R: int):
+        """The backward of _last_block_train_cls_rows down to dQKV.  dX[:R] arrives zero off the class rows and
+        leaves so (the ln_2 backward writes the class rows only), cls_dF's other rows are zero since allocation;
+        the dW / db products read those full-layout buffers as the full block would."""
+        N, H = self.N, self.H
+        dX = self.dX[:R]
+        dXc, dFc, dHc = dX[::L], self.cls_dF[:R][::L], self.dH[:R][::L]
+        ops.gemm_nt(dXc, self.wt(i, "mlp.c_proj.weight"), dFc, aux_in=self.Fp[i][::L], epilogue=ops.EPI_DGELU,
+                    tile=self.tile)
+        self._dw(dX, self.cls_G[:R], self.g(i, "mlp.c_proj.weight"), self.g(i, "mlp.c_proj.bias"))
+        ops.gemm_nt(dFc, self.wt(i, "mlp.c_fc.weight"), dHc, epilogue=ops.EPI_NONE, tile=self.tile)
+        self._dw(self.cls_dF[:R], self.cls_H2[:R], self.g(i, "mlp.c_fc.weight"), self.g(i, "mlp.c_fc.bias"))
+        # the full tower's dgamma / dbeta partials from the class rows (the other rows' dy is zero)
+        self.lnb.bwd(dHc, self.X1[i][::L], self.p(i, "ln_2.weight"), self.mean2[i][:N], self.rstd2[i][:N], dXc,
+                     self.g(i, "ln_2.weight"), self.g(i, "ln_2.bias"), dres=dXc, live=(1, L))
+        ops.gemm_nt(dXc, self.wt(i, "attn.out_proj.weight"), self.dO[:R][::L], epilogue=ops.EPI_NONE, tile=self.tile)
+        self._dw(dX, self.O[i], self.g(i, "attn.out_proj.weight"), self.g(i, "attn.out_proj.bias"))
+        ops.attention_bwd_rows(self.QKV[i], self.O[i], self.dO[:R], self.LSE[i], N, L, H, self.causal, 1,
+                               dqkv=self.dQKV[:R])
+
     def _dw(self, dY: torch.Tensor, Xin: torch.Tensor, dW: torch.Tensor, db: torch.Tensor):
         """dW[out,in] = dY^T . Xin (fp16 out; both operands read K-major in place, K = rows), db = colsum(dY).
         A live (EOT-truncated) tower first scatters both operands into the full row layout, so K and the
@@ -467,22 +534,25 @@ class _Tower:
             dX = self.dX[:R]
             dF, dH, dO, dQKV = self.dF[:R], self.dH[:R], self.dO[:R], self.dQKV[:R]
             trainable_w = i == last
-            # ---- MLP: X[i+1] = X1 + c_proj(gelu(c_fc(ln_2(X1))))
-            ops.gemm_nt(dX, self.wt(i, "mlp.c_proj.weight"), dF, aux_in=self.Fp[i], epilogue=ops.EPI_DGELU,
-                        tile=self.tile)
-            if trainable_w:
-                self._dw(dX, self.G[:R], self.g(i, "mlp.c_proj.weight"), self.g(i, "mlp.c_proj.bias"))
-            ops.gemm_nt(dF, self.wt(i, "mlp.c_fc.weight"), dH, epilogue=ops.EPI_NONE, tile=self.tile)
-            if trainable_w:
-                self._dw(dF, self.H2[:R], self.g(i, "mlp.c_fc.weight"), self.g(i, "mlp.c_fc.bias"))
-            self.lnb.bwd(dH, self.X1[i], self.p(i, "ln_2.weight"), self.mean2[i], self.rstd2[i], dX,
-                         self.g(i, "ln_2.weight"), self.g(i, "ln_2.bias"), dres=dX, live=self.live)
-            # ---- attention: X1 = X + out_proj(attn(ln_1(X)))
-            ops.gemm_nt(dX, self.wt(i, "attn.out_proj.weight"), dO, epilogue=ops.EPI_NONE, tile=self.tile)
-            if trainable_w:
-                self._dw(dX, self.O[i], self.g(i, "attn.out_proj.weight"), self.g(i, "attn.out_proj.bias"))
-            ops.attention_bwd(self.QKV[i], self.O[i], dO, self.LSE[i], N, L, H, self.causal, dqkv=dQKV,
-                              ws=self.attn_ws)
+            if trainable_w and self._cls_fwd:
+                self._last_block_bwd_cls_rows(i, L, R)
+            else:
+                # ---- MLP: X[i+1] = X1 + c_proj(gelu(c_fc(ln_2(X1))))
+                ops.gemm_nt(dX, self.wt(i, "mlp.c_proj.weight"), dF, aux_in=self.Fp[i], epilogue=ops.EPI_DGELU,
+                            tile=self.tile)
+                if trainable_w:
+                    self._dw(dX, self.G[:R], self.g(i, "mlp.c_proj.weight"), self.g(i, "mlp.c_proj.bias"))
+                ops.gemm_nt(dF, self.wt(i, "mlp.c_fc.weight"), dH, epilogue=ops.EPI_NONE, tile=self.tile)
+                if trainable_w:
+                    self._dw(dF, self.H2[:R], self.g(i, "mlp.c_fc.weight"), self.g(i, "mlp.c_fc.bias"))
+                self.lnb.bwd(dH, self.X1[i], self.p(i, "ln_2.weight"), self.mean2[i], self.rstd2[i], dX,
+                             self.g(i, "ln_2.weight"), self.g(i, "ln_2.bias"), dres=dX, live=self.live)
+                # ---- attention: X1 = X + out_proj(attn(ln_1(X)))
+                ops.gemm_nt(dX, self.wt(i, "attn.out_proj.weight"), dO, epilogue=ops.EPI_NONE, tile=self.tile)
+                if trainable_w:
+                    self._dw(dX, self.O[i], self.g(i, "attn.out_proj.weight"), self.g(i, "attn.out_proj.bias"))
+                ops.attention_bwd(self.QKV[i], self.O[i], dO, self.LSE[i], N, L, H, self.causal, dqkv=dQKV,
+                                  ws=self.attn_ws)
             ops.gemm_nt(dQKV, self.wt(i, "attn.in_proj_weight"), dH, epilogue=ops.EPI_NONE, tile=self.tile)
             if trainable_w:
                 self._dw(dQKV, self.H1[:R], self.g(i, "attn.in_proj_weight"), self.g(i, "attn.in_proj_bias"))
@@ -575,6 +645,10 @@ class MapleEngine:
                 t.fused_qkv_attn = t.tile == -1 and t.Rs[0] >= 2048
         # a forward-only engine's vision tower: ln_post reads the last block's output at the class rows only
         self.vis.cls_only = bool(cfg.inference) and not cfg.captions
+        # ... and a training engine's step runs that block on the class rows after its in-projection, forward and
+        # backward (vis.train_cls_rows; set it False for the full block: every result is bit for bit the same)
+        if not cfg.inference and not cfg.captions and self.Lv <= 224:
+            self.vis.enable_train_cls_rows()
         self.side = torch.cuda.Stream(device=self.device)
         self.overlap_towers = True  # False: both towers on the current stream (isolated kernel timing)
         self.vision_first = cfg.vision_first  # tower enqueue order after each fork (EngineConfig)
@@ -963,7 +1037,11 @@ class MapleEngine:
         side.wait_stream(main)
         with torch.cuda.stream(side):
             self.refresh_transposes(all_layers=False)
-        self.forward()  # joins the side stream before returning
+        self.vis._cls_pass = True  # the step's own forward: the last vision block on the class rows (train_cls_rows)
+        try:
+            self.forward()  # joins the side stream before returning
+        finally:
+            self.vis._cls_pass = False
         if self.soft_labels:
             ops.clip_loss_soft_fwd_bwd(self.img_feat, self.txt_feat, self.img_n, self.txt_n, self.norms,
                                        self.logits, self.soft_label_in, self.P["logit_scale"], self.dmm, self.cos_ws,

@@ -441,6 +441,28 @@ def attention_bwd(qkv, out, dout, lse, N, L, H, causal, dqkv=None, ws=None, ld_l
     return dqkv
 
 
+def attention_bwd_rows(qkv, out, dout, lse, N, L, H, causal, q_rows, dqkv=None, ld_lse=None):
+    """attention_bwd for a dout that is zero at query rows >= q_rows of every sequence: those rows of dout, out and
+    lse are not read (they may hold stale data), dqkv is written in full, bit for bit attention_bwd's for that dout.
+    Non-causal, L <= 224."""
+    if ld_lse is None:
+        ld_lse = L
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    ev = None
+    if _PROBE is not None and _PROBE.wants("attention"):
+        # the 32-query blocks below q_rows against every key (8 * 64 flop a pair); bytes: Q, dO, O of those blocks,
+        # K, V read, dQ, dK, dV written
+        rows = min(L, (q_rows + 31) // 32 * 32)
+        ev = _PROBE.around(8.0 * N * H * rows * L * 64, N * H * (2.0 * 5 * 64 * L + 2.0 * 3 * 64 * rows),
+                           f"attention_bwd_rows/L{L}")
+    call("mf_attention_bwd_rows", _p(qkv), _ld(qkv), _p(out), _ld(out), _p(dout), _ld(dout), _p(lse), ld_lse,
+         _p(dqkv), _ld(dqkv), N, L, H, int(causal), q_rows, _s())
+    if ev is not None:
+        ev.record()
+    return dqkv
+
+
 def im2col_patch(img, out, patch=16):
     B, C, R, R2 = img.shape
     assert C == 3 and R == R2 and img.is_contiguous()

@@ -130,6 +130,15 @@ int mf_qkv_attention_supported(int N, int L, int H, int causal);
 int mf_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out, int64_t ld_out, const void* dout,
                      int64_t ld_dout, const float* lse, float* dq_dot_ws, int ld_lse, void* dqkv, int64_t ld_dqkv,
                      int N, int L, int H, int causal, void* stream);
+/* mf_attention_bwd for a dout that is zero at query rows >= q_rows of every sequence (the training step's last
+ * vision block: ln_post reads the class token only, so one row of dO per image is live).  Rows >= q_rows of dout,
+ * out and lse are not read and may hold anything; qkv is read, and dqkv written, at every row.  dqkv is bit for bit
+ * mf_attention_bwd's for that dout (+0 in dQ at the other query rows).  Non-causal, L <= 224 only (the fused
+ * one-workgroup-per-head kernel); a causal mask or a longer sequence is an error -- there is no detour through the
+ * full path, which would read the rows this entry leaves alone.                                      */
+int mf_attention_bwd_rows(const void* qkv, int64_t ld_qkv, const void* out, int64_t ld_out, const void* dout,
+                          int64_t ld_dout, const float* lse, int ld_lse, void* dqkv, int64_t ld_dqkv, int N, int L,
+                          int H, int causal, int q_rows, void* stream);
 
 /* ---- token assembly / prompt injection (clip/model.py:514-538,320-349; trainers/maple.py:54,152-166) */
 int mf_im2col_patch(const void* img, int img_is_f32, void* out, int B, int R, int P, void* stream);
