@@ -49,6 +49,8 @@ SIGNATURES = {
     "mf_layernorm_bwd_inject": [P, L, P, L, P, P, P, P, L, P, L, P, I, I, P, I, I, I, P],
     "mf_layernorm_fwd_inject": [P, L, P, P, P, L, P, P, I, I, P, I, I, I, P],
     "mf_gemm_splitk": [P, L, I, P, L, I, P, L, I, I, I, P, L, I, I, P],
+    "mf_gemm_splitk_live": [P, L, I, P, L, I, P, L, I, I, I, P, L, I, I, I, I, I, P],
+    "mf_colsum_f16_live": [P, L, I, I, P, I, P, I, I, P],
     "mf_clip_loss_soft_fwd_bwd": [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "mf_argmax_correct": [P, I, I, P, P, P, P],
     "mf_optim_chunk_bytes": [],

@@ -288,12 +288,23 @@ __global__ __launch_bounds__(256) void transpose_kernel(const f16* __restrict__ 
 // ---------------------------------------------------------------- column sums (bias grads)
 // part[chunk][c] = sum of rows [64*chunk, 64*chunk+64) of column c: a block of 256 threads covers
 // 256 columns (4 per lane, 8-byte loads) x 64 rows (16 per wave); then col_reduce_kernel.
+// LIVE (mf_colsum_f16_live): rows r with r % l_full >= l_live are exact zeros, so a chunk without a live row sums
+// to +0 (0.f + -0.f = +0.f): it stores that without loading anything.
 constexpr int CS_ROWS = 64;
+template <bool LIVE>
 __global__ __launch_bounds__(256) void colsum_part_kernel(const f16* __restrict__ in, int64_t ld, int R, int C,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part, int l_live, int l_full) {
   __shared__ f32x4 red[4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 256 + lane * 4;
+  if constexpr (LIVE) {
+    // live iff the chunk's first row is live or the next sequence starts inside it (and inside the matrix)
+    const int rc = blockIdx.y * CS_ROWS, s = rc % l_full, nxt = rc + (l_full - s);
+    if (s >= l_live && (nxt >= rc + CS_ROWS || nxt >= R)) {
+      if (w == 0 && c < C) *(f32x4*)(part + (int64_t)blockIdx.y * C + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+      return;
+    }
+  }
   const int r0 = blockIdx.y * CS_ROWS + w * 16;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
   if (c < C) {
@@ -608,21 +619,40 @@ extern "C" int mf_transpose_f16(const void* in, int64_t ld_in, void* out, int64_
 
 extern "C" int mf_colsum_blocks(int R) { return (R + CS_ROWS - 1) / CS_ROWS; }
 
-extern "C" int mf_colsum_f16(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace,
-                             void* stream) {
+// l_full > 0: the live form.  out == NULL: the partials only (the caller reduces workspace [mf_colsum_blocks(R)][C]
+// later, mf_col_reduce_batch).
+static int colsum_run(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace, int l_live,
+                      int l_full, void* stream) {
   if (R <= 0 || C <= 0) return 0;
   const int nb = mf_colsum_blocks(R);
   hipStream_t st = (hipStream_t)stream;
   if (C % 4 || ld % 4) return mf_set_error("mf_colsum_f16: C and ld must be multiples of 4", -1);
   dim3 grid((C + 255) / 256, nb);
-  colsum_part_kernel<<<grid, 256, 0, st>>>((const f16*)in, ld, R, C, workspace);
+  if (l_full > 0) colsum_part_kernel<true><<<grid, 256, 0, st>>>((const f16*)in, ld, R, C, workspace, l_live, l_full);
+  else colsum_part_kernel<false><<<grid, 256, 0, st>>>((const f16*)in, ld, R, C, workspace, 0, 0);
   MF_CHECK_LAUNCH();
+  if (!out) return 0;
   if (out_f16)
     col_reduce_kernel<true><<<dim3((C + 63) / 64, 1), 1024, 0, st>>>(workspace, workspace, nb, C, C, out, out, 0);
   else
     col_reduce_kernel<false><<<dim3((C + 63) / 64, 1), 1024, 0, st>>>(workspace, workspace, nb, C, C, out, out, 0);
   MF_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int mf_colsum_f16(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace,
+                             void* stream) {
+  return colsum_run(in, ld, R, C, out, out_f16, workspace, 0, 0, stream);
+}
+
+// mf_colsum_f16 for an `in` whose rows r with r % L_full >= L_live are exact zeros (+0 or -0): the 64-row chunks
+// without a live row store +0 partials and read nothing; grid, partial layout and reduction are mf_colsum_f16's,
+// so out is bit for bit its result.
+extern "C" int mf_colsum_f16_live(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace,
+                                  int L_live, int L_full, void* stream) {
+  if (L_full <= 0 || L_live <= 0 || L_live > L_full || R % L_full != 0)
+    return mf_set_error("mf_colsum_f16_live: needs 0 < L_live <= L_full and R % L_full == 0", -1);
+  return colsum_run(in, ld, R, C, out, out_f16, workspace, L_live, L_full, stream);
 }
 
 extern "C" int mf_small_linear_fwd(const void* X, const void* W, const void* b, void* Y, int M, int I, int O,

@@ -48,6 +48,12 @@ struct GemmArgs {
                // N-major positions inside a slice (split_tile_of)
 };
 
+// the LIVE instantiation's arguments (mf_gemm_splitk_live): k-rows with k % l_full >= l_live are exact zeros in
+// A's columns m < m_live
+struct GemmArgsLive : GemmArgs {
+  int l_full, l_live, m_live;
+};
+
 // The QuickGELU pre-activation (EPI_BIAS_GELU's aux output) is read again only by the backward, so it is
 // stored non-temporally: it streams past the L2, which keeps the operand panels of the running tiles
 // (r02 same-box A/B, scripts/ab_gemm_dirs.sh: v.fc 661 -> 680 TFLOP/s isolated, the c4 step +1.2 %; the C
@@ -356,8 +362,13 @@ MF_DEV void dma_stage(const f16* A, int a_bytes, const f16* B, int b_bytes, f16*
     __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rsrc, (lds_ptr_t)(lb + b_dst[i]), 16, b_voff[i] + b_k, 0, 0, 0);
 }
 
-template <int BM, int BN, int WM, int WN, int S, int EPI, bool TA = false, bool TB = false>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmArgs g0) {
+// LIVE (split-K, both operands K-major): the K loop stages and consumes only the K-tiles that hold a live k-row
+// (GemmArgsLive), in ascending order through the same ring.  A dead tile's MFMAs add sums of
+// +-0 products to an accumulator that starts at +0 and can never become -0, so skipping it leaves every bit as it
+// was; a workgroup whose rows reach past m_live walks every tile.
+template <int BM, int BN, int WM, int WN, int S, int EPI, bool TA = false, bool TB = false, bool LIVE = false>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(std::conditional_t<LIVE, GemmArgsLive, GemmArgs> g0) {
+  static_assert(!LIVE || (TA && TB && EPI == EPI_F32), "the live K loop is the split-K weight-gradient tile's");
   GemmArgs g = g0;
   constexpr int NW = WM * WN;
   constexpr int NT = NW * 64;
@@ -387,6 +398,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmArgs g0) {
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
   const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   int mt, nt;
+  const int k_all = g.K;  // LIVE: the whole K axis
+  int kt0 = 0;            // LIVE: global index of this slice's first K-tile
   if (g.ksplit > 0) {  // split-K: this workgroup's K slice and partial-sum plane (EPI_F32)
     int z;
     if (legacy) {
@@ -396,6 +409,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmArgs g0) {
       split_tile_of(wgid, tiles_m, tiles_n, g.xb != 0, z, mt, nt);
     }
     const int k0 = z * g.ksplit;
+    kt0 = k0 / BK;
     g.A += (int64_t)k0 * (TA ? g.lda : 1);
     g.B += (int64_t)k0 * (TB ? g.ldb : 1);
     g.K = min(g.ksplit, g.K - k0);
@@ -431,27 +445,17 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmArgs g0) {
 
   MF_STAMP(0);
   const int nk = (g.K + BK - 1) / BK;  // a ragged last K step only with both operands K-major (zero-filled)
-  // prologue: S-1 stages in flight
+  // prologue: S-1 stages in flight (LIVE: its own below, of live tiles)
+  if constexpr (!LIVE) {
 #pragma unroll
-  for (int p = 0; p < S - 1; ++p)
-    if (p < nk) MF_STAGE(p, p * BK);
+    for (int p = 0; p < S - 1; ++p)
+      if (p < nk) MF_STAGE(p, p * BK);
+  }
 
   const int fr = lane & 15, fg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    // stage kt landed (this wave's DMA: leave the younger stages in flight), then one barrier:
-    // every wave's DMA for kt is visible and every wave is done reading stage kt-1's buffer
-    const int younger = min(S - 2, nk - 1 - kt);
-    if constexpr (S >= 3) {
-      if (younger >= 2) wait_vmcnt<2 * (A_INS + B_INS)>();
-      else if (younger == 1) wait_vmcnt<A_INS + B_INS>();
-      else wait_vmcnt<0>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    if (kt == 0) MF_STAMP(1);
-    if (kt + S - 1 < nk) MF_STAGE((kt + S - 1) % S, (kt + S - 1) * BK);
-    const f16* la = lds + (kt % S) * STAGE;
+  // the fragment reads and MFMAs of the K-tile in ring buffer `buf`
+  auto consume = [&](int buf) {
+    const f16* la = lds + buf * STAGE;
     const f16* lb = la + BM * BK;
     // fragments of sub-step 1 are read while the MFMAs of sub-step 0 run (register double buffer)
     f16x8 af[2][TM], bf[2][TN];
@@ -481,6 +485,61 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmArgs g0) {
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[s][j], af[s][i], acc[i][j], 0, 0, 0);
+  };
+  if constexpr (LIVE) {
+    // first live K-tile of this slice at or after local tile t (nk: none).  Tile t holds global k-rows
+    // r .. r + 63, r = (kt0 + t) * 64; it is live iff r % l_full < l_live or the next sequence starts inside it.
+    const bool dense = min(m0 + BM, g.M) > g0.m_live;  // A's columns >= m_live are ordinary data
+    auto next_live = [&](int t) {
+      if (dense || t >= nk) return t;
+      const int r = (kt0 + t) * BK;
+      const int s = r % g0.l_full;
+      if (s < g0.l_live) return t;
+      const int nxt = r + (g0.l_full - s);  // the next sequence's first k-row
+      return nxt >= k_all ? nk : nxt / BK - kt0;
+    };
+    int cur = next_live(0), issued = 0;
+#pragma unroll
+    for (int p = 0; p < S - 1; ++p)
+      if (cur < nk) {
+        MF_STAGE(p, cur * BK);
+        ++issued;
+        cur = next_live(cur + 1);
+      }
+    for (int i = 0; i < issued; ++i) {
+      const int younger = issued - 1 - i;  // stages issued after stage i and still in flight (<= S - 2)
+      if constexpr (S >= 3) {
+        if (younger >= 2) wait_vmcnt<2 * (A_INS + B_INS)>();
+        else if (younger == 1) wait_vmcnt<A_INS + B_INS>();
+        else wait_vmcnt<0>();
+      } else {
+        wait_vmcnt<0>();
+      }
+      __builtin_amdgcn_s_barrier();
+      if (cur < nk) {
+        MF_STAGE(issued % S, cur * BK);
+        ++issued;
+        cur = next_live(cur + 1);
+      }
+      consume(i % S);
+    }
+  } else {
+    for (int kt = 0; kt < nk; ++kt) {
+      // stage kt landed (this wave's DMA: leave the younger stages in flight), then one barrier:
+      // every wave's DMA for kt is visible and every wave is done reading stage kt-1's buffer
+      const int younger = min(S - 2, nk - 1 - kt);
+      if constexpr (S >= 3) {
+        if (younger >= 2) wait_vmcnt<2 * (A_INS + B_INS)>();
+        else if (younger == 1) wait_vmcnt<A_INS + B_INS>();
+        else wait_vmcnt<0>();
+      } else {
+        wait_vmcnt<0>();
+      }
+      __builtin_amdgcn_s_barrier();
+      if (kt == 0) MF_STAMP(1);
+      if (kt + S - 1 < nk) MF_STAGE((kt + S - 1) % S, (kt + S - 1) * BK);
+      consume(kt % S);
+    }
   }
 
 #undef MF_STAGE
@@ -1579,9 +1638,10 @@ extern "C" int mf_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb
 // dW = dY^T X, K = tokens): `splits` workgroups per 128x128 tile each reduce a K slice into an fp32
 // plane of ws (splits * M * N floats), then one pass sums the planes in a fixed order into C (fp16
 // when out_f16, else fp32).  splits <= 0 picks enough slices for ~2 workgroups per CU.
-extern "C" int mf_gemm_splitk(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
-                              void* C, int64_t ldc, int M, int N, int K, float* ws, int64_t ws_floats, int splits,
-                              int out_f16, void* stream) {
+// l_full > 0: the live form (mf_gemm_splitk_live), both operands K-major
+static int splitk_run(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
+                      int64_t ldc, int M, int N, int K, float* ws, int64_t ws_floats, int splits, int out_f16,
+                      int l_live, int l_full, int m_live, void* stream) {
   if (M <= 0 || N <= 0) return 0;
   const bool both_k = a_kmajor && b_kmajor;
   if (K <= 0 || (!both_k && (K % BK) != 0))
@@ -1607,8 +1667,12 @@ extern "C" int mf_gemm_splitk(const void* A, int64_t lda, int a_kmajor, const vo
   const bool slice_major = tiles >= 96;
   GemmArgs a{(const f16*)A, (const f16*)B, ws, nullptr, nullptr, nullptr, lda, ldb, (int64_t)N, 0, M, N, K, 1, ks,
              slice_major ? ((N > M) ? 1 : 0) : 2};
-  int rc;
-  if (a_kmajor && b_kmajor) rc = launch_tile<128, 128, 2, 2, 2, true, true>(a, EPI_F32, st);
+  int rc = 0;
+  if (l_full > 0) {
+    const GemmArgsLive al{a, l_full, l_live, m_live};
+    gemm_nt_kernel<128, 128, 2, 2, 2, EPI_F32, true, true, true><<<dim3(tiles * splits), dim3(256), 0, st>>>(al);
+    MF_CHECK_LAUNCH();
+  } else if (a_kmajor && b_kmajor) rc = launch_tile<128, 128, 2, 2, 2, true, true>(a, EPI_F32, st);
   else if (a_kmajor) rc = launch_tile<128, 128, 2, 2, 2, true, false>(a, EPI_F32, st);
   else if (b_kmajor) rc = launch_tile<128, 128, 2, 2, 2, false, true>(a, EPI_F32, st);
   else rc = launch_tile<128, 128, 2, 2, 2>(a, EPI_F32, st);
@@ -1617,6 +1681,30 @@ extern "C" int mf_gemm_splitk(const void* A, int64_t lda, int a_kmajor, const vo
   splitk_reduce_kernel<<<(unsigned)((nq + 255) / 256), 256, 0, st>>>(ws, splits, M, N, C, ldc, out_f16);
   MF_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int mf_gemm_splitk(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
+                              void* C, int64_t ldc, int M, int N, int K, float* ws, int64_t ws_floats, int splits,
+                              int out_f16, void* stream) {
+  return splitk_run(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, ws, ws_floats, splits, out_f16, 0, 0, 0,
+                    stream);
+}
+
+// mf_gemm_splitk for an A operand whose k-rows with k % L_full >= L_live are exact zeros (+0 or -0) in the output
+// rows m < m_live (the columns m of the K-major A; its columns >= m_live are ordinary data, B is only finite): the
+// 64-row K-tiles that hold no live k-row are neither loaded nor multiplied.  Slices, planes, the order inside a
+// slice and the slice sum are mf_gemm_splitk's, so the result is bit for bit its result; mf_gemm_splitk_ws_floats
+// sizes the workspace of both.  Both operands K-major, 0 < L_live <= L_full, K % L_full == 0.
+extern "C" int mf_gemm_splitk_live(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb,
+                                   int b_kmajor, void* C, int64_t ldc, int M, int N, int K, float* ws,
+                                   int64_t ws_floats, int splits, int out_f16, int L_live, int L_full, int m_live,
+                                   void* stream) {
+  if (!a_kmajor || !b_kmajor) return mf_set_error("mf_gemm_splitk_live: both operands must be K-major", -1);
+  if (L_full <= 0 || L_live <= 0 || L_live > L_full || K % L_full != 0)
+    return mf_set_error("mf_gemm_splitk_live: needs 0 < L_live <= L_full and K % L_full == 0", -1);
+  if (m_live < 0) return mf_set_error("mf_gemm_splitk_live: m_live < 0", -1);
+  return splitk_run(A, lda, 1, B, ldb, 1, C, ldc, M, N, K, ws, ws_floats, splits, out_f16, L_live, L_full,
+                    m_live > M ? M : m_live, stream);
 }
 
 extern "C" int mf_gemm_splitk_ws_floats(int M, int N, int K, int splits) {

@@ -502,8 +502,8 @@ extern "C" int mf_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int
 namespace {
 struct ColReduceDesc {
   const float* part;  // [nblk][C] partial sums
-  float* out;         // [C]
-  int nblk, C, accumulate, pad;
+  void* out;          // [C], fp32 or (out_f16) fp16
+  int nblk, C, accumulate, out_f16;
 };
 __global__ __launch_bounds__(1024) void col_reduce_batch_kernel(const ColReduceDesc* __restrict__ descs) {
   __shared__ float red[16][65];
@@ -528,7 +528,15 @@ __global__ __launch_bounds__(1024) void col_reduce_batch_kernel(const ColReduceD
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) s += red[k][lane];
-    d.out[c] = d.accumulate ? d.out[c] + s : s;
+    // both forms are col_reduce_kernel's line for line (mf_common.h): a deferred bias gradient (fp16) is bit for
+    // bit the one mf_colsum_f16 reduces itself
+    if (d.out_f16) {
+      f16* o = (f16*)d.out + c;
+      *o = d.accumulate ? (f16)((float)*o + s) : (f16)s;
+    } else {
+      float* o = (float*)d.out + c;
+      *o = d.accumulate ? *o + s : s;
+    }
   }
 }
 }  // namespace

@@ -288,7 +288,8 @@ class _Tower:
         # query side of its attention backward have one live row per image.  Every dW / db operand stays a
         # full-layout buffer whose dead rows are exact zeros (dX, cls_dF) or finite values that meet only zeros (O,
         # cls_G, cls_H2), so each sum keeps the full block's length and order and every gradient is bit for bit the
-        # full block's.  After such a step X[layers], X1[last] and O[last] hold this step's values at the class rows
+        # full block's; the split-K products and column sums skip the 64-row tiles of those buffers that hold no class
+        # row (_dw's dead=: adding +-0 to a sum that is never -0 changes nothing).  After such a step X[layers], X1[last] and O[last] hold this step's values at the class rows
         # only (O: rows 0..15 of each sequence); the public forward() / eval_batch() always run the full block.
         self.train_cls_rows = False
         self._cls_pass = False  # forward_loss() is running (read by forward())
@@ -340,9 +341,9 @@ class _Tower:
         # GEMM tile rule of this tower's projections: 0 = latency picks (the tower that sets the step), -1 =
         # work-per-CU-second picks (the tower beside it; MapleEngine.__init__ decides, csrc/gemm.hip text_tile)
         self.tile = 0
-        # this tower's LayerNorm dgamma/dbeta partials, reduced in one launch at the end of its backward
+        # this tower's LayerNorm dgamma/dbeta partials and its trainable block's bias-gradient partials (each with a
+        # workspace of its own), reduced in one launch at the end of its backward
         self.lnb = ops.LNGradBatch(dev)
-        self.cs_ws = e(ops.colsum_ws_floats(R if self.live is None else N * self.live[1], 4 * D), dt=F32)
         # split-K weight gradients of the trainable block (few output tiles, K = R tokens): fp32 partial
         # planes, summed in a fixed order (only where the automatic split count exceeds 1: few 128x128 output tiles)
         shapes = ((3 * D, D), (D, D), (4 * D, D), (D, 4 * D))
@@ -372,7 +373,7 @@ class _Tower:
         self.fused_qkv_attn = self.e.cfg.fused_qkv_attn in ("both", "vision" if self.name == "image_encoder"
                                                              else "text")
         self.tile = 0
-        self.lnb = self.cs_ws = self.dw_ws = None
+        self.lnb = self.dw_ws = None
         self.dw_split = set()
 
     # -- parameters of block i
@@ -491,21 +492,26 @@ class _Tower:
         dXc, dFc, dHc = dX[::L], self.cls_dF[:R][::L], self.dH[:R][::L]
         ops.gemm_nt(dXc, self.wt(i, "mlp.c_proj.weight"), dFc, aux_in=self.Fp[i][::L], epilogue=ops.EPI_DGELU,
                     tile=self.tile)
-        self._dw(dX, self.cls_G[:R], self.g(i, "mlp.c_proj.weight"), self.g(i, "mlp.c_proj.bias"))
+        self._dw(dX, self.cls_G[:R], self.g(i, "mlp.c_proj.weight"), self.g(i, "mlp.c_proj.bias"), dead=(1, L))
         ops.gemm_nt(dFc, self.wt(i, "mlp.c_fc.weight"), dHc, epilogue=ops.EPI_NONE, tile=self.tile)
-        self._dw(self.cls_dF[:R], self.cls_H2[:R], self.g(i, "mlp.c_fc.weight"), self.g(i, "mlp.c_fc.bias"))
+        self._dw(self.cls_dF[:R], self.cls_H2[:R], self.g(i, "mlp.c_fc.weight"), self.g(i, "mlp.c_fc.bias"),
+                 dead=(1, L))
         # the full tower's dgamma / dbeta partials from the class rows (the other rows' dy is zero)
         self.lnb.bwd(dHc, self.X1[i][::L], self.p(i, "ln_2.weight"), self.mean2[i][:N], self.rstd2[i][:N], dXc,
                      self.g(i, "ln_2.weight"), self.g(i, "ln_2.bias"), dres=dXc, live=(1, L))
         ops.gemm_nt(dXc, self.wt(i, "attn.out_proj.weight"), self.dO[:R][::L], epilogue=ops.EPI_NONE, tile=self.tile)
-        self._dw(dX, self.O[i], self.g(i, "attn.out_proj.weight"), self.g(i, "attn.out_proj.bias"))
+        self._dw(dX, self.O[i], self.g(i, "attn.out_proj.weight"), self.g(i, "attn.out_proj.bias"), dead=(1, L))
         ops.attention_bwd_rows(self.QKV[i], self.O[i], self.dO[:R], self.LSE[i], N, L, H, self.causal, 1,
                                dqkv=self.dQKV[:R])
 
-    def _dw(self, dY: torch.Tensor, Xin: torch.Tensor, dW: torch.Tensor, db: torch.Tensor):
-        """dW[out,in] = dY^T . Xin (fp16 out; both operands read K-major in place, K = rows), db = colsum(dY).
+    def _dw(self, dY: torch.Tensor, Xin: torch.Tensor, dW: torch.Tensor, db: torch.Tensor, dead=None):
+        """dW[out,in] = dY^T . Xin (fp16 out; both operands read K-major in place, K = rows), db = colsum(dY), the
+        latter reduced by lnb.finish() at the end of the tower's backward.
         A live (EOT-truncated) tower first scatters both operands into the full row layout, so K and the
-        summation order are the full tower's (its extra rows contribute exact zeros)."""
+        summation order are the full tower's (its extra rows contribute exact zeros).
+        dead = (L_live, L_full) (the class-row block): rows past L_live of each L_full-row sequence of dY are exact
+        zeros, so the split-K product and the column sum skip the 64-row tiles without a live row
+        (mf_gemm_splitk_live / mf_colsum_f16_live: bit for bit the plain results)."""
         if self.live is not None:
             Ll, Lf = self.live
             # exactness rests on full_dy / full_x rows t >= Ll staying zero: they are zeroed at allocation and the
@@ -516,10 +522,10 @@ class _Tower:
             dY = ops.seq_scatter(dY, self.full_dy[:, :dY.shape[1]], self.N, Ll, Lf)[:self.N * Lf]
             Xin = ops.seq_scatter(Xin, self.full_x[:, :Xin.shape[1]], self.N, Ll, Lf)[:self.N * Lf]
         if tuple(dW.shape) in self.dw_split:
-            ops.gemm_splitk(dY, Xin, dW, self.dw_ws, a_kmajor=True, b_kmajor=True)
+            ops.gemm_splitk(dY, Xin, dW, self.dw_ws, a_kmajor=True, b_kmajor=True, live=dead)
         else:
             ops.gemm(dY, Xin, dW, epilogue=ops.EPI_NONE, a_kmajor=True, b_kmajor=True)
-        ops.colsum(dY, db, self.cs_ws)
+        self.lnb.colsum(dY, db, live=dead)
 
     def backward(self, n_prompted: int, prompt_grads: List[torch.Tensor]):
         """self.dX[:Rs[-1]] holds d(loss)/d(X[layers]).  On return self.dX[:Rs[0]] = d(loss)/d(X[0]) (the
@@ -555,6 +561,8 @@ class _Tower:
                                   ws=self.attn_ws)
             ops.gemm_nt(dQKV, self.wt(i, "attn.in_proj_weight"), dH, epilogue=ops.EPI_NONE, tile=self.tile)
             if trainable_w:
+                # (under the class-row block the dQ third of dQKV is +0 off the class rows, but mf_gemm_splitk_live
+                # with m_live = D measured no faster than the plain product: the dense K / V workgroups set its time)
                 self._dw(dQKV, self.H1[:R], self.g(i, "attn.in_proj_weight"), self.g(i, "attn.in_proj_bias"))
             if 1 <= i <= n_prompted and not self.grow[i]:
                 # ln_1 backward + the deep prompt's gradient (its rows of dX) in one pass

@@ -169,9 +169,12 @@ def gemm_splitk_ws_floats(M: int, N: int, K: int, splits: int = 0) -> int:
     return n
 
 
-def gemm_splitk(A, B, C, ws, splits=0, a_kmajor=False, b_kmajor=False):
+def gemm_splitk(A, B, C, ws, splits=0, a_kmajor=False, b_kmajor=False, live=None, m_live=None):
     """C[M,N] = op(A) . op(B)^T with K split over workgroups and an fp32 workspace (mf_gemm_splitk):
-    for the weight gradients, few output tiles and K = tokens.  C fp16 or fp32."""
+    for the weight gradients, few output tiles and K = tokens.  C fp16 or fp32.
+    live = (L_live, L_full): the caller's promise that A's k-rows with k % L_full >= L_live are exact zeros in the
+    output rows m < m_live (default: all M); their K-tiles are skipped, the result is bit for bit the plain one
+    (mf_gemm_splitk_live, both operands K-major).  The probe prices it as the full product."""
     M, Ka = (A.shape[1], A.shape[0]) if a_kmajor else A.shape
     N, Kb = (B.shape[1], B.shape[0]) if b_kmajor else B.shape
     assert Ka == Kb, (A.shape, a_kmajor, B.shape, b_kmajor)
@@ -180,8 +183,13 @@ def gemm_splitk(A, B, C, ws, splits=0, a_kmajor=False, b_kmajor=False):
     ev = None
     if _PROBE is not None and _PROBE.wants("gemm"):
         ev = _PROBE.around(2.0 * M * N * K, _gemm_bytes(M, N, K, C), _gkey(), (M, N, K, "splitk"))
-    call("mf_gemm_splitk", _p(A), _ld(A), int(a_kmajor), _p(B), _ld(B), int(b_kmajor), _p(C), _ld(C), M, N, K,
-         _p(ws), ws.numel(), splits, int(C.dtype == torch.float16), _s())
+    if live is not None:
+        call("mf_gemm_splitk_live", _p(A), _ld(A), int(a_kmajor), _p(B), _ld(B), int(b_kmajor), _p(C), _ld(C), M, N,
+             K, _p(ws), ws.numel(), splits, int(C.dtype == torch.float16), live[0], live[1],
+             M if m_live is None else m_live, _s())
+    else:
+        call("mf_gemm_splitk", _p(A), _ld(A), int(a_kmajor), _p(B), _ld(B), int(b_kmajor), _p(C), _ld(C), M, N, K,
+             _p(ws), ws.numel(), splits, int(C.dtype == torch.float16), _s())
     if ev is not None:
         ev.record()
     return C
@@ -234,12 +242,13 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace=None, d
 class LNGradBatch:
     """Deferred dgamma/dbeta reductions of every LayerNorm backward of a pass: each LN param pair gets
     its own partial-sum workspace, and one mf_col_reduce_batch launch at the end of the backward
-    reduces them all (instead of one reduction launch per LayerNorm)."""
+    reduces them all (instead of one reduction launch per LayerNorm).  The trainable block's bias gradients
+    (colsum()) ride in the same launch."""
 
     def __init__(self, device):
         self.device = device
         self.ws = {}          # dgamma data_ptr -> workspace
-        self.descs = []       # (part_ptr, out_ptr, nblk, C)
+        self.descs = []       # (part_ptr, out_ptr, nblk, C[, out_f16])
         self.keys = []
         self.dev_descs = None
         self.max_cols = 0
@@ -343,6 +352,22 @@ class LNGradBatch:
         _rec(ev)
         return dx
 
+    def colsum(self, dy, db, live=None):
+        """db = colsum(dy) (a Linear's bias gradient, fp16 or fp32) with the reduction deferred to finish(): the
+        partials go to this db's own workspace, and the batch kernel sums them in mf_colsum_f16's order (bit for
+        bit its result).  live: see ops.colsum."""
+        R, C = dy.shape
+        key = ("db", db.data_ptr())
+        nblk = call("mf_colsum_blocks", R)
+        if key not in self.ws:
+            part = torch.empty(nblk * C, device=self.device, dtype=torch.float32)
+            self.ws[key] = part
+            self.descs.append((part.data_ptr(), db.data_ptr(), nblk, C, int(db.dtype == torch.float16)))
+            self.max_cols = max(self.max_cols, C)
+            self.dev_descs = None
+        assert self.ws[key].numel() == nblk * C and db.numel() == C
+        colsum(dy, None, self.ws[key], live=live)
+
     def finish(self):
         if not self.descs:
             return
@@ -351,9 +376,9 @@ class LNGradBatch:
             assert call("mf_col_reduce_desc_bytes") == 32
             arr = np.zeros(len(self.descs), dtype=np.dtype([("part", np.uint64), ("out", np.uint64),
                                                             ("nblk", np.int32), ("C", np.int32),
-                                                            ("acc", np.int32), ("pad", np.int32)]))
-            for i, (pp, op, nb, c) in enumerate(self.descs):
-                arr[i] = (pp, op, nb, c, 0, 0)
+                                                            ("acc", np.int32), ("out_f16", np.int32)]))
+            for i, (pp, op, nb, c, *f16) in enumerate(self.descs):
+                arr[i] = (pp, op, nb, c, 0, f16[0] if f16 else 0)
             self.dev_descs = torch.from_numpy(arr.view(np.uint8)).to(self.device)
         call("mf_col_reduce_batch", _p(self.dev_descs), len(self.descs), self.max_cols, _s())
 
@@ -528,11 +553,18 @@ def colsum_ws_floats(R: int, C: int) -> int:
     return call("mf_colsum_blocks", R) * C
 
 
-def colsum(inp, out, workspace=None):
+def colsum(inp, out, workspace=None, live=None):
+    """out[c] = sum_r inp[r, c].  out None: only the partials are written to workspace [colsum blocks of R][C] (reduced
+    later: LNGradBatch.colsum).  live = (L_live, L_full): the caller's promise that rows r with r % L_full >= L_live
+    are exact zeros (mf_colsum_f16_live, bit for bit the plain result)."""
     R, C = inp.shape
     if workspace is None:
         workspace = torch.empty(colsum_ws_floats(R, C), device=inp.device, dtype=torch.float32)
-    call("mf_colsum_f16", _p(inp), _ld(inp), R, C, _p(out), int(out.dtype == torch.float16), _p(workspace), _s())
+    f16 = int(out is not None and out.dtype == torch.float16)
+    if live is not None:
+        call("mf_colsum_f16_live", _p(inp), _ld(inp), R, C, _p(out), f16, _p(workspace), live[0], live[1], _s())
+    else:
+        call("mf_colsum_f16", _p(inp), _ld(inp), R, C, _p(out), f16, _p(workspace), _s())
     return out
 
 

@@ -59,6 +59,15 @@ int mf_gemm_splitk(const void* A, int64_t lda, int a_kmajor, const void* B, int6
                    int64_t ldc, int M, int N, int K, float* ws, int64_t ws_floats, int splits, int out_f16,
                    void* stream);
 int mf_gemm_splitk_ws_floats(int M, int N, int K, int splits);
+/* mf_gemm_splitk with a promise about A: its k-rows with k % L_full >= L_live are exact zeros (+0 or -0) in the
+ * output rows m < m_live (A's columns >= m_live are ordinary data; B is only finite).  The 64-row K-tiles that
+ * hold no live k-row are skipped by the workgroups below m_live; slices, planes and both summation orders are
+ * mf_gemm_splitk's, so C is bit for bit its result (the class-row block's weight gradients, K = N images x L
+ * tokens with one live row per image).  Both operands K-major (anything else is an error), 0 < L_live <= L_full,
+ * K % L_full == 0; workspace as mf_gemm_splitk.                                                              */
+int mf_gemm_splitk_live(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
+                        int64_t ldc, int M, int N, int K, float* ws, int64_t ws_floats, int splits, int out_f16,
+                        int L_live, int L_full, int m_live, void* stream);
 
 /* ---- LayerNorm (fp16 io, fp32 math; clip/model.py:153-159) --------------------------------
  * row_index (optional, int32): output row i normalises input row row_index[i]
@@ -100,9 +109,10 @@ int mf_layernorm_bwd_live(const void* dy, int64_t lddy, const void* x, int64_t l
                           int row0, int nrows, void* stream);
 
 /* dgamma == dbeta == NULL: write the per-block partials only; their reduction is deferred to one
- * mf_col_reduce_batch over all LayerNorms of a backward pass.  desc = {const float* part; float* out;
- * int nblk, C, accumulate, pad} (mf_col_reduce_desc_bytes() bytes each, device memory):
- * out[c] (=|+=) sum_b part[b*C + c], fixed order.                                                  */
+ * mf_col_reduce_batch over all LayerNorms of a backward pass.  desc = {const float* part; void* out;
+ * int nblk, C, accumulate, out_f16} (mf_col_reduce_desc_bytes() bytes each, device memory):
+ * out[c] (=|+=) sum_b part[b*C + c], fixed order; out is fp32, or fp16 when out_f16 (the deferred bias
+ * gradients: mf_colsum_f16 with out == NULL leaves the partials, and this sum is bit for bit its own).  */
 int mf_col_reduce_desc_bytes(void);
 int mf_col_reduce_batch(const void* descs, int n, int max_cols, void* stream);
 
@@ -172,8 +182,13 @@ int mf_transpose_f16(const void* in, int64_t ld_in, void* out, int64_t ld_out, i
 int mf_seq_scatter(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int N, int L_live, int L_full, int C,
                    void* stream);
 int mf_colsum_blocks(int R);
-/* out[c] = sum_r in[r,c]; workspace: mf_colsum_blocks(R) * C floats                               */
+/* out[c] = sum_r in[r,c]; workspace: mf_colsum_blocks(R) * C floats.  out == NULL: only the partials
+ * workspace[mf_colsum_blocks(R)][C] are written, for a later mf_col_reduce_batch (nblk = mf_colsum_blocks(R)).  */
 int mf_colsum_f16(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace, void* stream);
+/* mf_colsum_f16 for an `in` whose rows r with r % L_full >= L_live are exact zeros: the 64-row chunks without a
+ * live row store +0 partials and read nothing; bit for bit mf_colsum_f16's result.  R % L_full == 0.          */
+int mf_colsum_f16_live(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace,
+                       int L_live, int L_full, void* stream);
 int mf_cast_f16_f32(const void* in, float* out, int64_t n, void* stream);
 
 /* ---- prompt-learner linears, M <= 16 rows (trainers/maple.py:111-131,194-215) --------------- */
