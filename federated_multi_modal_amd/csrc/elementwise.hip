@@ -529,6 +529,9 @@ extern "C" int mf_vision_assemble(const void* patch, const float* cls, const flo
                                   void* x, int B, int G2, int n_ctx, int D, void* stream) {
   if (B <= 0) return 0;
   if (D % 4) return mf_set_error("mf_vision_assemble: D % 4", -1);
+  // 8-byte accesses (4 fp16) to patch, shared_ctx and x; cls and pos are read one float at a time
+  if ((uintptr_t)patch % 8 || (uintptr_t)shared_ctx % 8 || (uintptr_t)x % 8)
+    return mf_set_error("mf_vision_assemble: 8-byte aligned patch, shared_ctx and x required", -1);
   const int64_t total = (int64_t)B * (G2 + 1 + n_ctx) * (D / 4);
   vision_assemble_kernel<<<nblk(total), 256, 0, (hipStream_t)stream>>>(
       (const f16*)patch, cls, pos, (const f16*)shared_ctx, (f16*)x, B, G2, n_ctx, D);
@@ -540,6 +543,8 @@ extern "C" int mf_text_assemble(const void* prefix, const void* ctx, const void*
                                 int K, int L, int n_ctx, int D, void* stream) {
   if (K <= 0) return 0;
   if (D % 4) return mf_set_error("mf_text_assemble: D % 4", -1);
+  if ((uintptr_t)prefix % 8 || (uintptr_t)ctx % 8 || (uintptr_t)suffix % 8 || (uintptr_t)x % 8)
+    return mf_set_error("mf_text_assemble: 8-byte aligned prefix, ctx, suffix and x required", -1);
   const int64_t total = (int64_t)K * L * (D / 4);
   text_assemble_kernel<<<nblk(total), 256, 0, (hipStream_t)stream>>>(
       (const f16*)prefix, (const f16*)ctx, (const f16*)suffix, pos, (f16*)x, K, L, n_ctx, D);
@@ -551,7 +556,7 @@ extern "C" int mf_text_assemble(const void* prefix, const void* ctx, const void*
 // not part of the C ABI of include/mapfed.h
 extern "C" int mf_prompt_inject_fwd_ld(void* x, int64_t ldx, const float* prompt, int N, int L, int row0, int nrows,
                                        int D, void* stream) {
-  if (N <= 0) return 0;
+  if (N <= 0 || nrows <= 0) return 0;
   if (row0 < 0 || row0 + nrows > L) return mf_set_error("mf_prompt_inject_fwd: rows out of range", -1);
   if (ldx < D) return mf_set_error("mf_prompt_inject_fwd: ldx < D", -1);
   inject_kernel<<<nblk((int64_t)N * nrows * D), 256, 0, (hipStream_t)stream>>>((f16*)x, ldx, prompt, N, L, row0,
@@ -567,8 +572,11 @@ extern "C" int mf_prompt_inject_fwd(void* x, const float* prompt, int N, int L, 
 
 extern "C" int mf_prompt_inject_bwd(void* dx, int N, int L, int row0, int nrows, int D, void* out, int out_f16,
                                     int accumulate, int zero_rows, void* stream) {
+  if (N <= 0 || nrows <= 0) return 0;
   if (row0 < 0 || row0 + nrows > L) return mf_set_error("mf_prompt_inject_bwd: rows out of range", -1);
   if (D % 4) return mf_set_error("mf_prompt_inject_bwd: D % 4", -1);
+  // dx is read (and zeroed) 4 fp16 at a time; out is written one element at a time
+  if ((uintptr_t)dx % 8) return mf_set_error("mf_prompt_inject_bwd: 8-byte aligned dx required", -1);
   inject_bwd_kernel<<<dim3((D + 255) / 256, nrows), 1024, 0, (hipStream_t)stream>>>((f16*)dx, N, L, row0, nrows, D,
                                                                                     out, out_f16, accumulate,
                                                                                     zero_rows);
@@ -580,6 +588,9 @@ extern "C" int mf_seq_grow(const void* src, void* dst, const void* cap, const fl
                            int n_ctx, int D, void* stream) {
   if (N <= 0) return 0;
   if (D % 8 || Lp < n_ctx || ncap < 0 || n_ctx < 0) return mf_set_error("mf_seq_grow: bad shape", -1);
+  // 16-byte accesses (8 fp16) to src, dst and cap; prompt is read one float at a time
+  if ((uintptr_t)src % 16 || (uintptr_t)dst % 16 || (uintptr_t)cap % 16)
+    return mf_set_error("mf_seq_grow: 16-byte aligned src, dst and cap required", -1);
   const int L = Lp + ncap;
   const int64_t total = (int64_t)N * L * (D / 8);
   seq_grow_kernel<<<nblk(total), 256, 0, (hipStream_t)stream>>>((const f16*)src, (f16*)dst, (const f16*)cap, prompt,
@@ -590,7 +601,9 @@ extern "C" int mf_seq_grow(const void* src, void* dst, const void* cap, const fl
 
 extern "C" int mf_seq_grow_bwd(const void* ddst, void* dsrc, int N, int Lp, int ncap, int n_ctx, int D, void* stream) {
   if (N <= 0) return 0;
-  if (D % 8 || Lp < n_ctx || ncap < 0) return mf_set_error("mf_seq_grow_bwd: bad shape", -1);
+  if (D % 8 || Lp < n_ctx || ncap < 0 || n_ctx < 0) return mf_set_error("mf_seq_grow_bwd: bad shape", -1);
+  if ((uintptr_t)ddst % 16 || (uintptr_t)dsrc % 16)
+    return mf_set_error("mf_seq_grow_bwd: 16-byte aligned ddst and dsrc required", -1);
   const int64_t total = (int64_t)N * Lp * (D / 8);
   seq_grow_bwd_kernel<<<nblk(total), 256, 0, (hipStream_t)stream>>>((const f16*)ddst, (f16*)dsrc, N, Lp, Lp + ncap,
                                                                    n_ctx, D);
@@ -611,6 +624,7 @@ extern "C" int mf_caption_pool(const int* tokens, int B, int T, const float* tab
 extern "C" int mf_transpose_f16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int R, int C,
                                 void* stream) {
   if (R <= 0 || C <= 0) return 0;
+  if (ld_in < C || ld_out < R) return mf_set_error("mf_transpose_f16: ld_in >= C and ld_out >= R required", -1);
   dim3 grid((C + 63) / 64, (R + 63) / 64);
   transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const f16*)in, ld_in, (f16*)out, ld_out, R, C);
   MF_CHECK_LAUNCH();
@@ -627,6 +641,11 @@ static int colsum_run(const void* in, int64_t ld, int R, int C, void* out, int o
   const int nb = mf_colsum_blocks(R);
   hipStream_t st = (hipStream_t)stream;
   if (C % 4 || ld % 4) return mf_set_error("mf_colsum_f16: C and ld must be multiples of 4", -1);
+  if (ld < C) return mf_set_error("mf_colsum_f16: ld < C", -1);
+  if (!workspace) return mf_set_error("mf_colsum_f16: null workspace", -1);
+  // 8-byte loads (4 fp16) of in, 16-byte stores (4 floats) of the partials
+  if ((uintptr_t)in % 8 || (uintptr_t)workspace % 16)
+    return mf_set_error("mf_colsum_f16: 8-byte aligned in and 16-byte aligned workspace required", -1);
   dim3 grid((C + 255) / 256, nb);
   if (l_full > 0) colsum_part_kernel<true><<<grid, 256, 0, st>>>((const f16*)in, ld, R, C, workspace, l_live, l_full);
   else colsum_part_kernel<false><<<grid, 256, 0, st>>>((const f16*)in, ld, R, C, workspace, 0, 0);

@@ -151,6 +151,13 @@ int mf_attention_bwd_rows(const void* qkv, int64_t ld_qkv, const void* out, int6
                           int H, int causal, int q_rows, void* stream);
 
 /* ---- token assembly / prompt injection (clip/model.py:514-538,320-349; trainers/maple.py:54,152-166) */
+/* Refused (nonzero, mf_last_error(), nothing launched) unless the stated preconditions hold; empty work (a batch
+ * or row count of 0) returns 0 and launches nothing.
+ * mf_im2col_patch: R % P == 0, P % 8 == 0, img and out 16-byte aligned.
+ * mf_vision_assemble / mf_text_assemble: D % 4 == 0; the fp16 operands (patch, shared_ctx, x / prefix, ctx, suffix,
+ *   x) 8-byte aligned (they are accessed 4 elements at a time); cls and pos need only their natural alignment.
+ * mf_prompt_inject_fwd / _bwd: 0 <= row0 and row0 + nrows <= L; N == 0 or nrows == 0 is empty work.  _bwd: D % 4 == 0
+ *   and dx 8-byte aligned.                                                                                          */
 int mf_im2col_patch(const void* img, int img_is_f32, void* out, int B, int R, int P, void* stream);
 int mf_vision_assemble(const void* patch, const float* cls, const float* pos, const void* shared_ctx, void* x,
                        int B, int G2, int n_ctx, int D, void* stream);
@@ -165,7 +172,8 @@ int mf_prompt_inject_bwd(void* dx, int N, int L, int row0, int nrows, int D, voi
 /* ---- caption-conditioned visual prompts (K19; clip/model.py:457-476, 550-561; trainers/maple.py:307-322) */
 /* The growing vision sequence of a prompted layer: dst [N, Lp+ncap, D] = src rows 0..Lp-n_ctx-1 | cap    */
 /* [ncap, D] (fp16, shared by every sequence) | fp16(prompt [n_ctx, D] fp32); replaces the torch.cat of   */
-/* clip/model.py:324-330 fed with cat(projected captions, deep prompt) (:558-559)                          */
+/* clip/model.py:324-330 fed with cat(projected captions, deep prompt) (:558-559).  Both directions need   */
+/* D % 8 == 0, 0 <= n_ctx <= Lp, ncap >= 0 and 16-byte aligned fp16 operands (8 elements per access).      */
 int mf_seq_grow(const void* src, void* dst, const void* cap, const float* prompt, int N, int Lp, int ncap, int n_ctx,
                 int D, void* stream);
 /* its backward into the previous output: dsrc [N, Lp, D] = ddst rows 0..Lp-n_ctx-1, zeros for the dropped */
@@ -176,6 +184,8 @@ int mf_seq_grow_bwd(const void* ddst, void* dsrc, int N, int Lp, int ncap, int n
 /* [0, vocab) reads nothing and makes its caption's pooled row NaN (the step's loss check then raises)      */
 int mf_caption_pool(const int* tokens, int B, int T, const float* table, int vocab, const void* w, int D,
                     void* pooled, void* stream);
+/* out [C, R] = in [R, C]^T; ld_in >= C and ld_out >= R (refused otherwise).  Any alignment: 16-byte tile accesses
+ * are used only when both pointers are 16-byte aligned and both leading dimensions are multiples of 8.       */
 int mf_transpose_f16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int R, int C, void* stream);
 /* dst row n*L_full + t = src row n*L_live + t (t < L_live; other dst rows untouched), C % 8 == 0 columns: the
  * EOT-truncated text tower's block-11 weight-gradient operands in the full tower's row layout              */
@@ -183,7 +193,9 @@ int mf_seq_scatter(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, i
                    void* stream);
 int mf_colsum_blocks(int R);
 /* out[c] = sum_r in[r,c]; workspace: mf_colsum_blocks(R) * C floats.  out == NULL: only the partials
- * workspace[mf_colsum_blocks(R)][C] are written, for a later mf_col_reduce_batch (nblk = mf_colsum_blocks(R)).  */
+ * workspace[mf_colsum_blocks(R)][C] are written, for a later mf_col_reduce_batch (nblk = mf_colsum_blocks(R)).
+ * Refused unless C % 4 == 0, ld % 4 == 0, ld >= C, in is 8-byte aligned (4 fp16 per load) and workspace is non-null
+ * and 16-byte aligned (4 floats per store); mf_colsum_f16_live likewise.                                         */
 int mf_colsum_f16(const void* in, int64_t ld, int R, int C, void* out, int out_f16, float* workspace, void* stream);
 /* mf_colsum_f16 for an `in` whose rows r with r % L_full >= L_live are exact zeros: the 64-row chunks without a
  * live row store +0 partials and read nothing; bit for bit mf_colsum_f16's result.  R % L_full == 0.          */
@@ -194,6 +206,8 @@ int mf_cast_f16_f32(const void* in, float* out, int64_t n, void* stream);
 /* ---- prompt-learner linears, M <= 16 rows (trainers/maple.py:111-131,194-215) --------------- */
 int mf_small_linear_fwd(const void* X, const void* W, const void* b, void* Y, int M, int I, int O, int is_f16,
                         void* stream);
+/* dX, dW and db may each be null; db is written by the dW kernel, so a null dW leaves db untouched (in the batched
+ * form too).                                                                                                     */
 int mf_small_linear_bwd(const void* dY, const void* X, const void* W, void* dX, void* dW, void* db, int M, int I,
                         int O, int is_f16, int accumulate_dx, void* stream);
 
