@@ -1286,7 +1286,9 @@ extern "C" int mf_attention_bwd_rows(const void* qkv, int64_t ld_qkv, const void
   if (L <= 0 || L > 224) return mf_set_error("mf_attention_bwd_rows: 0 < L <= 224 required", -1);
   if (causal) return mf_set_error("mf_attention_bwd_rows: causal masks are not supported", -1);
   if (q_rows <= 0 || q_rows > L) return mf_set_error("mf_attention_bwd_rows: 0 < q_rows <= L required", -1);
-  if (ld_lse < L || (ld_qkv % 8) || (ld_out % 8) || (ld_dout % 8) || (ld_dqkv % 4))
+  // ld_out % 4 as mf_attention_fwd, which writes out, asks (and as mf_attention_bwd takes it): out is read by plain
+  // 16-byte global loads in phase 0, which need no more than the 8-byte row alignment the forward's stores have
+  if (ld_lse < L || (ld_qkv % 8) || (ld_out % 4) || (ld_dout % 8) || (ld_dqkv % 4))
     return mf_set_error("mf_attention_bwd_rows: bad strides", -1);
   const int LP = padded_len(L);
   hipStream_t st = (hipStream_t)stream;
