@@ -201,14 +201,6 @@ MF_DEV void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// s_waitcnt vmcnt(n) lgkmcnt(0): LDS-DMA of all but the n youngest VMEM ops landed AND every ds_read
-// of this wave completed (a buffer's readers are done before the barrier that follows)
-template <int N>
-MF_DEV void wait_vm_lgkm0() {
-  static_assert(N >= 0 && N < 64, "vmcnt");
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
-
 // s_waitcnt vmcnt(n) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4]=7 | lgkmcnt[11:8]=15 | vmcnt[5:4]<<14)
 template <int N>
 MF_DEV void wait_vmcnt() {
@@ -551,183 +543,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(std::conditional_
 }
 
 // ------------------------------------------------------------------------------------------------
-// gemm8: 8 waves (512 threads), BM x BN tile with BM = 256 (or 128), one workgroup per CU.
-// Why this shape: a CU pulls operands from L2 at roughly 64-70 GB/s (MI355X_MICROARCH.md, LDS gather
-// rates), so the tile's FLOP per fetched byte sets the MFMA ceiling: 128x128 needs ~150 GB/s per CU
-// at full MFMA rate (measured main loop 45-50 % of peak), 256x256 needs ~75 GB/s.
-// Pipeline (cdna_hip_programming.md §5 T3+T4, restated for this kernel): a K-tile (BK = 64) is four
-// phases (m-half, k-sub) in the order (0,0) (1,0) (1,1) (0,1); a phase issues the ds_reads of the
-// NEXT phase's fragments (from data retired by an earlier barrier) ahead of its own MFMAs, so LDS
-// latency hides under the matrix pipe.  The operands of a K-tile are four half-tiles
-// [A k0, B k0, A k1, B k1] (sequence number 4*kt + h), each a [rows][32] fp16 image (64-byte rows,
-// 16-byte chunk c of row r stored at c ^ ((-(r >> 2)) & 3): conflict-free ds_read_b128 fragment
-// reads, checked with the bank model).  They live in a ring of NSLOT = 10 slots of SLOT bytes
-// (160 KiB) and are filled by LDS-DMA (buffer_load ... lds, 16 rows x 64 B per wave instruction,
-// swizzle applied to the source) TWO K-tiles ahead, one half-tile per phase: ~8 phases of latency
-// cover before a counted vmcnt + barrier retires a pair (two such points per K-tile).  WAR: the
-// half-tile a load overwrites (sequence - 10) was last read at least one barrier earlier and every
-// ds_read completes (lgkmcnt(0)) before the next barrier.  A/B fragment register sets alternate
-// statically (no copies, no scratch); the loop is peeled so the steady-state body has no branches.
-template <int BM, int BN, int WM, int WN, int EPI>
-__global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs g) {
-  constexpr int NT = 512;
-  static_assert(WM * WN == 8, "8 waves");
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int QM = WTM / 2;
-  constexpr int QTM = QM / 16, TN = WTN / 16, TM = 2 * QTM;
-  static_assert(QTM >= 1 && TN >= 1 && QM % 16 == 0, "phase shape");
-  constexpr int A_INS = BM / 128;  // LDS-DMA wave instructions per wave per half-tile (rows x 64 B)
-  constexpr int B_INS = BN / 128;
-  static_assert(A_INS * 128 == BM && B_INS * 128 == BN, "half-tile split");
-  constexpr int HK = 32;                                // k-sub width (elements)
-  constexpr int SLOT = (BM > BN ? BM : BN) * HK;        // fp16 elements per ring slot
-  constexpr int NSLOT = 10;
-  constexpr int LDC = BN + 8;
-  constexpr int LDS_ELEMS = NSLOT * SLOT > BM * LDC ? NSLOT * SLOT : BM * LDC;
-  static_assert(LDS_ELEMS * 2 <= 160 * 1024, "LDS");
-  __shared__ __attribute__((aligned(1024))) f16 lds[LDS_ELEMS];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-
-  const int tiles_n = (g.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  int mt, nt;
-  tile_of(wgid, (g.M + BM - 1) / BM, tiles_n, g.xb, mt, nt);
-  const int m0 = mt * BM;
-  const int n0 = nt * BN;
-
-  // LDS-DMA: instruction covers 16 rows x 64 B; lane l -> row (l >> 2), chunk (l & 3), whose source
-  // chunk is pre-swizzled; rows past M (N) read as zero through the buffer descriptor's range (every
-  // offset is in the range-checked VGPR offset, none in the scalar offset).
-  const int src_chunk = (lane & 3) ^ ((-(lane >> 4)) & 3);
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.A, 0, (int)(((int64_t)(g.M - 1) * g.lda + g.K) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.B, 0, (int)(((int64_t)(g.N - 1) * g.ldb + g.K) * 2), 0x00020000);
-  const int a_voff = ((lane >> 2) * (int)g.lda + src_chunk * 8) * 2;
-  const int b_voff = ((lane >> 2) * (int)g.ldb + src_chunk * 8) * 2;
-  auto slot = [&](int seq) { return lds + (seq % NSLOT) * SLOT; };
-  // issue half-tile h (0: A k0, 1: B k0, 2: A k1, 3: B k1) of K-tile kt
-  auto issue = [&](int kt, int h) {
-    f16* dst = slot(4 * kt + h);
-    const int kofs = kt * BK + HK * (h >> 1);
-    if ((h & 1) == 0) {
-#pragma unroll
-      for (int i = 0; i < A_INS; ++i) {
-        const int row = (wid * A_INS + i) * 16;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)(dst + row * HK), 16,
-                                                 a_voff + (int)(((int64_t)(m0 + row) * g.lda + kofs) * 2), 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < B_INS; ++i) {
-        const int row = (wid * B_INS + i) * 16;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rsrc, (lds_ptr_t)(dst + row * HK), 16,
-                                                 b_voff + (int)(((int64_t)(n0 + row) * g.ldb + kofs) * 2), 0, 0, 0);
-      }
-    }
-  };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fg = lane >> 4;
-  // fragment (row, k 8*fg..8*fg+7 of the k-sub) of a [rows][32] image: row = base16 + fr
-  const int frag_off = fr * HK + ((fg ^ ((-(fr >> 2)) & 3)) << 3);
-  auto read_a = [&](f16x8 (&af)[QTM], const f16* img, int mh) {
-#pragma unroll
-    for (int i = 0; i < QTM; ++i) af[i] = *(const f16x8*)(img + (wm * WTM + mh * QM + i * 16) * HK + frag_off);
-  };
-  auto read_b = [&](f16x8 (&bf)[TN], const f16* img) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bf[j] = *(const f16x8*)(img + (wn * WTN + j * 16) * HK + frag_off);
-  };
-  auto mma = [&](const f16x8 (&af)[QTM], const f16x8 (&bf)[TN], int mh) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < QTM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[mh * QTM + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[mh * QTM + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  const int nk = g.K / BK;  // >= 2 (the launcher routes K = 64 elsewhere)
-  MF_STAMP(0);
-  // prologue: K-tiles 0 and 1 (eight half-tiles); retire A k0, B k0 of K-tile 0 and read phase 0's
-  // fragments A(0, k0), B(k0)
-#pragma unroll
-  for (int h = 0; h < 4; ++h) issue(0, h);
-#pragma unroll
-  for (int h = 0; h < 4; ++h) issue(1, h);
-  f16x8 fx[QTM], fy[QTM], fb0[TN], fb1[TN];
-  wait_vm_lgkm0<3 * A_INS + 3 * B_INS>();
-  lds_barrier();
-  read_a(fx, slot(0), 0);
-  read_b(fb0, slot(1));
-  MF_STAMP(1);
-
-  // one K-tile.  MODE 0: steady state (issues K-tile kt+2);  MODE 1: kt = nk-2 (nothing left to
-  // issue);  MODE 2: kt = nk-1 (the last).  The vmcnt of a retire point = wave instructions issued
-  // after the retired pair.
-  auto ktile = [&](int kt, auto mode_tag) {
-    constexpr int MODE = decltype(mode_tag)::value;
-    const f16* a0 = slot(4 * kt + 0);
-    const f16* a1 = slot(4 * kt + 2);
-    const f16* b1 = slot(4 * kt + 3);
-    // phase 0 (m-half 0, k0): next reads A(1, k0)
-    read_a(fy, a0, 1);
-    if constexpr (MODE == 0) issue(kt + 2, 0);
-    mma(fx, fb0, 0);
-    // retire A k1, B k1 of this K-tile
-    wait_vm_lgkm0<MODE == 0 ? 3 * A_INS + 2 * B_INS : (MODE == 1 ? 2 * A_INS + 2 * B_INS : 0)>();
-    lds_barrier();
-    // phase 1 (m-half 1, k0): next reads A(1, k1), B(k1)
-    read_a(fx, a1, 1);
-    read_b(fb1, b1);
-    if constexpr (MODE == 0) issue(kt + 2, 1);
-    mma(fy, fb0, 1);
-    // phase 2 (m-half 1, k1): next reads A(0, k1)
-    read_a(fy, a1, 0);
-    if constexpr (MODE == 0) issue(kt + 2, 2);
-    mma(fx, fb1, 1);
-    if constexpr (MODE != 2) {
-      // retire A k0, B k0 of the next K-tile
-      wait_vm_lgkm0<MODE == 0 ? 3 * A_INS + 2 * B_INS : A_INS + B_INS>();
-      lds_barrier();
-      // phase 3 (m-half 0, k1): next reads A(0, k0), B(k0) of the next K-tile
-      read_a(fx, slot(4 * kt + 4), 0);
-      read_b(fb0, slot(4 * kt + 5));
-      if constexpr (MODE == 0) issue(kt + 2, 3);
-    }
-    mma(fy, fb1, 0);
-  };
-  for (int kt = 0; kt < nk - 2; ++kt) ktile(kt, std::integral_constant<int, 0>{});
-  ktile(nk - 2, std::integral_constant<int, 1>{});
-  ktile(nk - 1, std::integral_constant<int, 2>{});
-  MF_STAMP(2);
-
-  __syncthreads();  // every wave is done with the operand ring (no DMA outstanding after the last K-tile)
-  epilogue_store<BM, BN, NT, TM, TN, EPI>(g, lds, acc, m0, n0, wm * WTM, wn * WTN, tid, fr, fg);
-  MF_STAMP(3);
-}
-
-
-// gemm8s: the 256x256 8-wave tile with the two wave rows (wm = 0, 1) staggered by one barrier (ping-pong,
-// cdna_hip_programming.md §5 "The 256² 8-phase template"): every phase is a memory section (fragment
-// ds_reads for this phase's MFMAs, one half-tile of LDS-DMA, the retire waits) and a compute section
-// (16 MFMAs), separated by barriers; wave row 1 runs one barrier behind row 0, so on each SIMD one wave
-// issues MFMAs while its partner loads.  Ring of 10 half-tile slots, half-tile H issued in the memory
-// section of phase H - 7.  With the stagger (derivation in DESIGN.md §6):
+// gemm8s (tile 20, not picked by the heuristic): the kernel gemm8f (below) replaced in r05, kept as the A/B baseline
+// the bit-identity test compares gemm8f with.  Tile, waves, phase order and stagger are gemm8f's (its header
+// describes them); the operand images differ: a K-tile is four half-tiles [A k0, B k0, A k1, B k1] (H = 4t + h),
+// each a [256 rows][32 k] fp16 image (64-byte rows, 16-byte chunk c of row r stored at c ^ ((-(r >> 2)) & 3):
+// conflict-free ds_read_b128 fragment reads), filled by LDS-DMA of 16 rows x 64 B per wave instruction (swizzle
+// applied to the source).  Ring of 10 half-tile slots, half-tile H issued in the memory section of phase H - 7.
+// With the stagger (derivation in DESIGN.md §6):
 //   RAW: a half-tile first read in phase f is retired (counted vmcnt) at the end of memory section f - 1;
 //   WAR: a slot last read in phase q is refilled in phase q + 2 or later (H - 10 is last read in phase
 //        <= H - 9, refilled in H - 7).
@@ -873,18 +695,32 @@ __global__ __launch_bounds__(512) void gemm8s_kernel(GemmArgs g) {
   MF_STAMP(3);
 }
 
-// gemm8f: the 256x256 8-wave staggered tile of gemm8s with FULL-LINE operand images.  gemm8s stages
-// [256 rows][32 k] half-tiles, so each LDS-DMA wave instruction covers 16 rows x 64 B: half of 16 cache lines,
-// each line fetched twice per K-tile (once per k-sub) -- its TA address/command FIFOs run full 4x as often as
-// hipBLASLt's (r04 PMC).  Here a half-tile is 128 rows x the whole K-tile ([128][64] fp16, 128-B rows, 16-B chunk
-// c of row r at c ^ (r & 7): the 4-wave kernel's conflict-free image), so an instruction covers 8 whole lines
-// (cdna_hip_programming.md §5 "The 256² 8-phase template": 128-row halves of A and B, BK = 64).  Half-tiles of
-// K-tile t, in issue order: H = 4t + {0: B rows 0-127, 1: B rows 128-255, 2: A rows 0-127, 3: A rows 128-255};
-// wave (wm, wn) reads A half wm and B half wn >> 1.  Phases (m-half, k-sub) as gemm8s, so every accumulator sums
-// its k-subs in ascending order: bit-identical to gemm8s and to the 4-wave tiles.  Ring of NSLOT = 10 half-tile
-// slots (160 KiB), half-tile H issued in the memory section of phase H - E (E = 6), K-tile t+1's four half-tiles
-// retired (vmcnt(2 half-tiles), then the barrier) in the memory section of phase 4t + 3.  Hazards under the
-// one-barrier stagger (row 1 runs a barrier behind row 0; row r's memory section of phase P lies between barrier
+// gemm8f: the 256x256 tile on 8 waves (512 threads, 2 wave rows wm x 4 wave columns wn, each wave a 128x64 block
+// of 16x16 MFMA tiles), one workgroup per CU (its operand ring is the CU's 160 KiB of LDS).
+// Why this shape: a CU pulls operands from L2 at roughly 64-70 GB/s (MI355X_MICROARCH.md, LDS gather rates), so
+// the tile's FLOP per fetched byte sets the MFMA ceiling: 128x128 needs ~150 GB/s per CU at full MFMA rate
+// (measured main loop 45-50 % of peak), 256x256 needs ~75 GB/s.
+// Pipeline (cdna_hip_programming.md §5 "The 256² 8-phase template"): a K-tile (BK = 64) is four phases (m-half,
+// k-sub) in the order (0,0) (1,0) (1,1) (0,1): m-half = a 64-row half of the wave's 128 rows, k-sub = a 32-deep
+// half of the K-tile, 16 MFMAs per phase.  Neighbouring phases share the B fragments of their k-sub (read in
+// phases 0 and 2 only), and every accumulator sums k-sub 0 before k-sub 1.  Each phase is a memory section (the
+// ds_reads of this phase's fragments, one half-tile of LDS-DMA, in phase 3 the counted vmcnt that retires the next
+// K-tile), a barrier, a compute section (the 16 MFMAs at raised priority) and a barrier.  Wave row 1 runs one
+// barrier behind row 0 (the stagger: one extra barrier before its first phase, one after row 0's last), so on each
+// SIMD, which holds one wave of each row, one wave issues MFMAs while its partner loads.
+// Operand images are FULL-LINE: a half-tile is 128 rows x the whole K-tile ([128][64] fp16, 128-B rows, 16-B chunk
+// c of row r at c ^ (r & 7): the 4-wave kernel's conflict-free image), so an LDS-DMA wave instruction covers 8
+// whole cache lines.  ([256 rows][32 k] images, one per k-sub, cover half of 16 lines per instruction and fetch
+// every line twice per K-tile; the TA address/command FIFOs then run full 4x as often as hipBLASLt's: r04 PMC,
+// DESIGN.md §4.)  Half-tiles of K-tile t, in issue order: H = 4t + {0: B rows 0-127, 1: B rows 128-255, 2: A rows
+// 0-127, 3: A rows 128-255}; wave (wm, wn) reads A half wm and B half wn >> 1.
+// Every output element is one chain of v_mfma_f32_16x16x32_f16 from a zero accumulator over k ascending in 32-deep
+// steps, with the 4-wave kernel's operand order (weight fragment first) and k-to-lane mapping (lane group fg holds
+// k 8 fg .. 8 fg + 7 of each k-sub), and the epilogue is epilogue_store: bit-identical to the 4-wave tiles
+// (tests/test_kernels_gpu.py, test_gemm8f_matches_4wave_tile).
+// Ring of NSLOT = 10 half-tile slots (160 KiB), half-tile H issued in the memory section of phase H - E (E = 6),
+// K-tile t+1's four half-tiles retired (vmcnt(2 half-tiles), then the barrier) in the memory section of phase
+// 4t + 3.  Hazards under the one-barrier stagger (row r's memory section of phase P lies between barrier
 // instances 2P + r and 2P + r + 1, its reads complete before instance 2P + r + 2):
 //   RAW: both rows' waits for K-tile t precede instance 8t, the first read of row 0 follows it;
 //   WAR: B halves are last read in phase 4t + 2 (both rows), A0 in 4t + 3 (row 0), A1 in 4t + 3 (row 1); the slot
@@ -1036,283 +872,27 @@ __global__ __launch_bounds__(512) void gemm8f_kernel(GemmArgs g) {
   MF_STAMP(3);
 }
 
-// gemm8p: gemm8f made persistent for launches of many rounds of 256x256 tiles (the eval engine's products at
-// EVAL_GROUP 4, M = 79 600; the C5 text tower, M = 77 000).  In-kernel stamps of gemm8f on those launches
-// (tests/diagnostics/gemm_stamps.cpp, profiles/r06_v6_gemm_stamps_eval4.txt): a 12-K-step tile lives ~29 us, of
-// which the prologue (the first K-tile's DMA round trip) is ~4 us and the epilogue ~4-7 us, and a new workgroup
-// starts ~3 us after its predecessor ends -- with one 160 KB workgroup per CU nothing else runs meanwhile.  Here one
-// workgroup per CU walks its XCD's tiles (the positions tile_of gives the XCD), and where the epilogue reads no
-// global operand (EPI_NONE / EPI_BIAS / EPI_BIAS_GELU) the NEXT tile's first six half-tiles are issued into the
-// (by then free) ring before this tile's epilogue, whose results go straight from registers to buffer stores (no
-// LDS staging; rows past M fall outside the buffer range and are dropped, so every wave issues the same count and
-// the counted vmcnt stays exact).  Epilogues that read aux (residual, QuickGELU') run before the next prologue:
-// a plain load while LDS-DMA is in flight would make the compiler drain it.  Main loop, fragment reads, MFMA
-// order and the epilogue arithmetic are gemm8f's / epilogue_store's: bit-identical (tests/test_kernels_gpu.py).
-// Needs N % 256 == 0, K % 64 == 0, fp16 C, 16-byte aligned C / aux with 8-element strides (the host checks).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// s_waitcnt lgkmcnt(0) alone (vmcnt 63 = no wait): this wave's ds_reads / ds_writes done, LDS-DMA left in flight
-MF_DEV void wait_lgkm0() { __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14)); }
-
-// gemm8p's epilogue while the next tile's first six half-tiles fly into ring slots 0..5: the tile's two 128-row
-// halves in turn staged through slots 6..9 ([128][256] fp16, 16-byte chunk c of row r at c ^ (r & 7)) by the four
-// waves that own the half, then every thread streams 16-byte chunks out (full cache lines) through buffer stores
-// (rows past M fall outside the range: dropped, so each thread issues exactly 8 stores per half, 8 more for the
-// pre-activation).  The arithmetic is epilogue_store's: fp16(acc + bias), then epi8's QuickGELU.
-template <int EPI>
-MF_DEV void epilogue_staged8p(const GemmArgs& g, f16* stage, const f32x4 (&acc)[8][4], const f16x4 (&bv)[4], int m0,
-                              int n0, int wm, int wn, int tid, int fr, int fg, __amdgpu_buffer_rsrc_t c_rsrc,
-                              __amdgpu_buffer_rsrc_t x_rsrc) {
-  static_assert(EPI == EPI_NONE || EPI == EPI_BIAS || EPI == EPI_BIAS_GELU, "epilogues without a global read");
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-    if (wm == hh) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int r = i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int col = wn * 64 + j * 16 + 4 * fg;
-          f16x4 t;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) t[e] = (f16)(acc[i][j][e] + (float)bv[j][e]);
-            else t[e] = (f16)acc[i][j][e];
-          }
-          *(f16x4*)(stage + r * 256 + ((((col >> 3) ^ (r & 7))) << 3) + (col & 7)) = t;
-        }
-      }
-    }
-    wait_lgkm0();
-    lds_barrier();
-#pragma unroll
-    for (int pass = 0; pass < 8; ++pass) {
-      const int r = pass * 16 + (tid >> 5), c = tid & 31;
-      const f16x8 tv = *(const f16x8*)(stage + r * 256 + ((c ^ (r & 7)) << 3));
-      const int m = m0 + hh * 128 + r, n = n0 + 8 * c;
-      f16x8 out;
-      if constexpr (EPI == EPI_NONE || EPI == EPI_BIAS) {
-        out = tv;
-      } else {
-        if (g.aux_out)  // the pre-activation, non-temporal (st16_stream's policy)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tv), x_rsrc,
-                                                 (int)(((int64_t)m * g.ld_aux + n) * 2), 0, 2);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float t2;
-          out[e] = (f16)quick_gelu16((float)tv[e], &t2);
-        }
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, out), c_rsrc,
-                                             (int)(((int64_t)m * g.ldc + n) * 2), 0, 0);
-    }
-    wait_lgkm0();
-    lds_barrier();  // the staging area is read before the next half (or the next tile's DMA) overwrites it
-  }
-}
-
-template <int EPI>
-__global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs g) {
-  constexpr int BM = 256, BN = 256, WN = 4;
-  constexpr int WTM = 128, WTN = 64, QTM = 4, TN = 4, TM = 8;
-  constexpr int HALF = 128 * BK;
-  constexpr int NSLOT = 10, E = 6;
-  static_assert(!epi_reads_aux<EPI>(), "epilogues that read a global operand stay on gemm8f");
-  static_assert(NSLOT * HALF * 2 <= 160 * 1024 && BM * (BN + 8) <= NSLOT * HALF && 128 * 256 <= 4 * HALF, "LDS");
-  __shared__ __attribute__((aligned(1024))) f16 lds[NSLOT * HALF];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid / WN, wn = wid % WN;
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = g.N / BN;
-  const int T = tiles_m * tiles_n;
-  // this workgroup's positions: XCD x's contiguous range (the bijective remap of the one-shot kernels), every
-  // nl-th position from l
-  const int x = blockIdx.x & 7, l = blockIdx.x >> 3, nl = gridDim.x >> 3;
-  const int q8 = T >> 3, r8 = T & 7;
-  const int pstart = x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
-  const int psize = q8 + (x < r8 ? 1 : 0);
-  int k = l;
-  if (k >= psize) return;  // whole workgroup
-
-  const int lrow = lane >> 3, schunk = (lane & 7) ^ lrow;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.A, 0, (int)(((int64_t)(g.M - 1) * g.lda + g.K) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.B, 0, (int)(((int64_t)(g.N - 1) * g.ldb + g.K) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      g.C, 0, (int)(((int64_t)(g.M - 1) * g.ldc + g.N) * 2), 0x00020000);
-  const void* xptr = (const void*)g.aux_out;
-  const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)xptr, 0, xptr ? (int)(((int64_t)(g.M - 1) * g.ld_aux + g.N) * 2) : 0, 0x00020000);
-  const int a_voff = (lrow * (int)g.lda + schunk * 8) * 2;
-  const int b_voff = (lrow * (int)g.ldb + schunk * 8) * 2;
-  auto slot = [&](int h) { return lds + (h % NSLOT) * HALF; };
-  int m0, n0;
-  auto tile_at = [&](int kk, int& mm0, int& nn0) {
-    int mt, nt;
-    tile_of(pstart + kk, tiles_m, tiles_n, g.xb, mt, nt);
-    mm0 = mt * BM;
-    nn0 = nt * BN;
-  };
-  auto issue = [&](int H, int mm0, int nn0) {
-    f16* dst = slot(H);
-    const int kofs = (H >> 2) * BK;
-    const int hh = H & 3;
-    if (hh < 2) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = (wid * 2 + i) * 8;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            b_rsrc, (lds_ptr_t)(dst + row * BK), 16,
-            b_voff + (int)(((int64_t)(nn0 + hh * 128 + row) * g.ldb + kofs) * 2), 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = (wid * 2 + i) * 8;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            a_rsrc, (lds_ptr_t)(dst + row * BK), 16,
-            a_voff + (int)(((int64_t)(mm0 + (hh - 2) * 128 + row) * g.lda + kofs) * 2), 0, 0, 0);
-      }
-    }
-  };
-
-  f32x4 acc[TM][TN];
-  const int fr = lane & 15, fg = lane >> 4;
-  const int foff0 = fr * BK + ((fg ^ (fr & 7)) << 3);
-  const int foff1 = fr * BK + (((4 + fg) ^ (fr & 7)) << 3);
-  const int a_row0 = 0, b_row0 = (wn & 1) * WTN;
-  auto read_a = [&](f16x8 (&af)[QTM], const f16* img, int mh, int foff) {
-#pragma unroll
-    for (int i = 0; i < QTM; ++i) af[i] = *(const f16x8*)(img + (a_row0 + mh * 64 + i * 16) * BK + foff);
-  };
-  auto read_b = [&](f16x8 (&bf)[TN], const f16* img, int foff) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bf[j] = *(const f16x8*)(img + (b_row0 + j * 16) * BK + foff);
-  };
-  auto mma = [&](const f16x8 (&af)[QTM], const f16x8 (&bf)[TN], int mh) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < QTM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[mh * QTM + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[mh * QTM + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  const int nk = g.K / BK;  // >= 2
-  f16x8 fx[QTM], fy[QTM], fb0[TN], fb1[TN];
-  auto ktile = [&](int kt, auto mode_tag) {
-    constexpr int MODE = decltype(mode_tag)::value;
-    const int h0 = 4 * kt;
-    const f16* ia = slot(h0 + 2 + wm);
-    const f16* ib = slot(h0 + (wn >> 1));
-    read_a(fx, ia, 0, foff0);
-    read_b(fb0, ib, foff0);
-    if constexpr (MODE <= 1) issue(h0 + E, m0, n0);
-    lds_barrier();
-    mma(fx, fb0, 0);
-    lds_barrier();
-    read_a(fy, ia, 1, foff0);
-    if constexpr (MODE <= 1) issue(h0 + E + 1, m0, n0);
-    lds_barrier();
-    mma(fy, fb0, 1);
-    lds_barrier();
-    read_a(fx, ia, 1, foff1);
-    read_b(fb1, ib, foff1);
-    if constexpr (MODE == 0) issue(h0 + E + 2, m0, n0);
-    lds_barrier();
-    mma(fx, fb1, 1);
-    lds_barrier();
-    read_a(fy, ia, 0, foff1);
-    if constexpr (MODE == 0) {
-      issue(h0 + E + 3, m0, n0);
-      wait_vmcnt<2 * 2>();
-    } else if constexpr (MODE == 1) {
-      wait_vmcnt<0>();
-    }
-    lds_barrier();
-    mma(fy, fb1, 0);
-    lds_barrier();
-  };
-
-  tile_at(k, m0, n0);
-#pragma unroll
-  for (int h = 0; h < E; ++h) issue(h, m0, n0);
-  wait_vmcnt<2 * 2>();
-  lds_barrier();
-  if (wm == 1) lds_barrier();  // the stagger
-#pragma unroll 1
-  for (;;) {
-    f16x4 bv[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU)
-        bv[j] = *(const f16x4*)(g.bias + n0 + wn * WTN + j * 16 + 4 * fg);
-      else
-        bv[j] = f16x4{};
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < nk - 2; ++kt) ktile(kt, std::integral_constant<int, 0>{});
-    ktile(nk - 2, std::integral_constant<int, 1>{});
-    ktile(nk - 1, std::integral_constant<int, 2>{});
-    if (wm == 0) lds_barrier();  // even out the barrier count: every wave is past its last ring read
-    const int kn = k + nl;
-    const bool more = kn < psize;
-    int m1 = 0, n1 = 0;
-    if (more) tile_at(kn, m1, n1);
-    if (more) {  // the next tile's prologue, under this tile's epilogue
-#pragma unroll
-      for (int h = 0; h < E; ++h) issue(h, m1, n1);
-    }
-    epilogue_staged8p<EPI>(g, lds + 6 * HALF, acc, bv, m0, n0, wm, wn, tid, fr, fg, c_rsrc, x_rsrc);
-    if (!more) break;
-    // the next tile's first K-tile: all but its last two half-tiles' loads and this epilogue's stores
-    if (EPI == EPI_BIAS_GELU && g.aux_out) wait_vmcnt<2 * 2 + 32>();
-    else wait_vmcnt<2 * 2 + 16>();
-    lds_barrier();
-    if (wm == 1) lds_barrier();  // the stagger
-    k = kn;
-    m0 = m1;
-    n0 = n1;
-  }
-}
-
-int launch_tile8f(const GemmArgs& a, int epi, hipStream_t st);
-
-int launch_tile8p(const GemmArgs& a, int epi, hipStream_t st) {
-  const int tiles = ((a.M + 255) / 256) * (a.N / 256);
-  const int grid = std::min(tiles, mf_cu_count()) / 8 * 8;
-  if (epi == EPI_F32 || !a.vec8 || a.N % 256 || grid < 8 || (int64_t)a.M * a.ldc * 2 >= (1ll << 31) ||
-      (int64_t)a.M * a.ld_aux * 2 >= (1ll << 31))
-    return mf_set_error("mf_gemm: persistent 256x256 tile needs fp16 C, N % 256 == 0, >= 8 tiles, < 2 GB", -2);
-  switch (epi) {
-    case EPI_NONE: gemm8p_kernel<EPI_NONE><<<grid, 512, 0, st>>>(a); break;
-    case EPI_BIAS: gemm8p_kernel<EPI_BIAS><<<grid, 512, 0, st>>>(a); break;
-    case EPI_BIAS_GELU: gemm8p_kernel<EPI_BIAS_GELU><<<grid, 512, 0, st>>>(a); break;
-    default: return launch_tile8f(a, epi, st);  // residual / QuickGELU' epilogues: gemm8f (bit-identical)
-  }
-  MF_CHECK_LAUNCH();
-  return 0;
-}
+// The epilogue dispatch of every launcher: the seven cases of its switch (epi), LAUNCH(E) being the launcher's own
+// kernel launch with the epilogue E as a template argument (the launchers stay plain functions and function
+// templates, see launch_kmajor)
+#define MF_EPI_CASES(LAUNCH)                          \
+  case EPI_NONE: LAUNCH(EPI_NONE); break;             \
+  case EPI_BIAS: LAUNCH(EPI_BIAS); break;             \
+  case EPI_BIAS_RESID: LAUNCH(EPI_BIAS_RESID); break; \
+  case EPI_BIAS_GELU: LAUNCH(EPI_BIAS_GELU); break;   \
+  case EPI_DGELU: LAUNCH(EPI_DGELU); break;           \
+  case EPI_F32: LAUNCH(EPI_F32); break;               \
+  case EPI_RESID: LAUNCH(EPI_RESID); break;
 
 int launch_tile8s(const GemmArgs& a, int epi, hipStream_t st) {
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
   dim3 grid(tiles), block(512);
+#define MF_8S(E) gemm8s_kernel<E><<<grid, block, 0, st>>>(a)
   switch (epi) {
-    case EPI_NONE: gemm8s_kernel<EPI_NONE><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS: gemm8s_kernel<EPI_BIAS><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_RESID: gemm8s_kernel<EPI_BIAS_RESID><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_GELU: gemm8s_kernel<EPI_BIAS_GELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_DGELU: gemm8s_kernel<EPI_DGELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_F32: gemm8s_kernel<EPI_F32><<<grid, block, 0, st>>>(a); break;
-    case EPI_RESID: gemm8s_kernel<EPI_RESID><<<grid, block, 0, st>>>(a); break;
-    default: return mf_set_error("mf_gemm_nt: bad epilogue", -2);
+    MF_EPI_CASES(MF_8S)
+    default: return mf_set_error("mf_gemm: bad epilogue", -2);
   }
+#undef MF_8S
   MF_CHECK_LAUNCH();
   return 0;
 }
@@ -1320,16 +900,12 @@ int launch_tile8s(const GemmArgs& a, int epi, hipStream_t st) {
 int launch_tile8f(const GemmArgs& a, int epi, hipStream_t st) {
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
   dim3 grid(tiles), block(512);
+#define MF_8F(E) gemm8f_kernel<E><<<grid, block, 0, st>>>(a)
   switch (epi) {
-    case EPI_NONE: gemm8f_kernel<EPI_NONE><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS: gemm8f_kernel<EPI_BIAS><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_RESID: gemm8f_kernel<EPI_BIAS_RESID><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_GELU: gemm8f_kernel<EPI_BIAS_GELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_DGELU: gemm8f_kernel<EPI_DGELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_F32: gemm8f_kernel<EPI_F32><<<grid, block, 0, st>>>(a); break;
-    case EPI_RESID: gemm8f_kernel<EPI_RESID><<<grid, block, 0, st>>>(a); break;
-    default: return mf_set_error("mf_gemm_nt: bad epilogue", -2);
+    MF_EPI_CASES(MF_8F)
+    default: return mf_set_error("mf_gemm: bad epilogue", -2);
   }
+#undef MF_8F
   MF_CHECK_LAUNCH();
   return 0;
 }
@@ -1402,40 +978,16 @@ __global__ __launch_bounds__(SM_NW * 64) void gemm_sm_kernel(GemmArgs g) {
 int launch_small_m(const GemmArgs& a, int epi, hipStream_t st) {
   if (a.M > 64 || a.K > 12 * 32 * SM_NW) return mf_set_error("mf_gemm: tile 50 needs M <= 64 and K <= 3072", -2);
   dim3 grid((a.N + 15) / 16, (a.M + 31) / 32), block(SM_NW * 64);
-#define MF_SM(E)                                                       \
-  case E:                                                              \
+#define MF_SM(E)                                                                \
+  do {                                                                          \
     if (a.K <= 4 * 32 * SM_NW) gemm_sm_kernel<4, E><<<grid, block, 0, st>>>(a); \
-    else gemm_sm_kernel<12, E><<<grid, block, 0, st>>>(a);             \
-    break;
+    else gemm_sm_kernel<12, E><<<grid, block, 0, st>>>(a);                      \
+  } while (0)
   switch (epi) {
-    MF_SM(EPI_NONE)
-    MF_SM(EPI_BIAS)
-    MF_SM(EPI_BIAS_RESID)
-    MF_SM(EPI_BIAS_GELU)
-    MF_SM(EPI_DGELU)
-    MF_SM(EPI_F32)
-    MF_SM(EPI_RESID)
+    MF_EPI_CASES(MF_SM)
     default: return mf_set_error("mf_gemm: bad epilogue", -2);
   }
 #undef MF_SM
-  MF_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch_tile8(const GemmArgs& a, int epi, hipStream_t st) {
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  dim3 grid(tiles), block(512);
-  switch (epi) {
-    case EPI_NONE: gemm8_kernel<BM, BN, WM, WN, EPI_NONE><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS: gemm8_kernel<BM, BN, WM, WN, EPI_BIAS><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_RESID: gemm8_kernel<BM, BN, WM, WN, EPI_BIAS_RESID><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_GELU: gemm8_kernel<BM, BN, WM, WN, EPI_BIAS_GELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_DGELU: gemm8_kernel<BM, BN, WM, WN, EPI_DGELU><<<grid, block, 0, st>>>(a); break;
-    case EPI_F32: gemm8_kernel<BM, BN, WM, WN, EPI_F32><<<grid, block, 0, st>>>(a); break;
-    case EPI_RESID: gemm8_kernel<BM, BN, WM, WN, EPI_RESID><<<grid, block, 0, st>>>(a); break;
-    default: return mf_set_error("mf_gemm_nt: bad epilogue", -2);
-  }
   MF_CHECK_LAUNCH();
   return 0;
 }
@@ -1445,19 +997,16 @@ int launch_tile(const GemmArgs& a, int epi, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int splits = a.ksplit > 0 ? (a.K + a.ksplit - 1) / a.ksplit : 1;
   dim3 grid(tiles * splits), block(WM * WN * 64);
+#define MF_NT(E) gemm_nt_kernel<BM, BN, WM, WN, S, E, TA, TB><<<grid, block, 0, st>>>(a)
   switch (epi) {
-    case EPI_NONE: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_NONE, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_BIAS, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_RESID: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_BIAS_RESID, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_BIAS_GELU: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_BIAS_GELU, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_DGELU: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_DGELU, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_F32: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_F32, TA, TB><<<grid, block, 0, st>>>(a); break;
-    case EPI_RESID: gemm_nt_kernel<BM, BN, WM, WN, S, EPI_RESID, TA, TB><<<grid, block, 0, st>>>(a); break;
+    MF_EPI_CASES(MF_NT)
     default: return mf_set_error("mf_gemm: bad epilogue", -2);
   }
+#undef MF_NT
   MF_CHECK_LAUNCH();
   return 0;
 }
+#undef MF_EPI_CASES
 
 // K-major operand combinations run on the 4-wave kernel's 128x128 / 128x64 / 64x64 tiles (a plain
 // function: kernel templates instantiated only through nested function templates lose their host
@@ -1566,7 +1115,7 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
     if (M <= 64 && K <= 3072)
       tile = 50;  // gemm_sm: the class-row block's products and the head projections (bit-identical to the tiles)
     else if (t256 >= 192 && t256 <= 256 && K >= 512)
-      tile = 40;  // one round of 256x256 tiles on one workgroup per CU (vision QKV: 225 tiles), gemm8s
+      tile = 40;  // one round of 256x256 tiles on one workgroup per CU (vision QKV: 225 tiles), gemm8f
     else if (M >= 16384 && K >= 512)  // the C5 text tower (M = 77 000): many rounds of tiles whatever the
       // shape, so the tile's own efficiency decides (gemm_bench.py ... c5): the full-line 256x256 kernel for
       // N >= 1536 or K >= 1024 (r05, profiles/r05_v1_gemm8f_c5.txt: c5.dh 878 -> 946, c5.dqkv 832 -> 905, c5.proj
@@ -1574,10 +1123,7 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
       // 735 / 663 on 160x128 / 256x256); r06: the eval engine's out-projection (M = 79 600 at EVAL_GROUP 4, N = K =
       // 768) 711..741 on 256x256 against 692..700 on 160x128 (profiles/r06_v1_gemm_eval4_*.txt, r06_v2_*)
       tile = (N >= 1536 || K >= 1024 || (N >= 768 && K >= 768)) ? 40 : 10;
-      // r06: the persistent gemm8p (tile 41) is faster isolated on these launches (eval4 qkv 951 -> 975, fc 811 ->
-      // 858, c5.qkv 789 -> 842 TFLOP/s, profiles/r06_v7_gemm8p_*.txt) but slower in the engine: eval pass 22 700 ->
-      // 20 900 img/s, C5 1 261 -> 1 145 img/s (same box, interleaved, profiles/r06_v8_gemm8p_engine_ab.txt), so
-      // it is not routed
+      // r06: a persistent 256x256 variant was faster isolated here but 8-10 % slower in the engine
     else if (M >= 4096 && K >= 512)  // vision products (M = 6368), tests/diagnostics/gemm_bench.py:
       // N = 3072: 160x128 (960 tiles); N = 768: 96x128 (402 tiles, two workgroups per CU) for K >= 2048,
       // 160x64 (480 tiles) for K = 768; +6..37 % over the 128-row tiles
@@ -1598,31 +1144,22 @@ extern "C" int mf_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, 
     } else
       tile = t128 >= 512 ? 1 : (t128 >= 256 ? 2 : 3);
   }
-  // tile ids: the ones the heuristic picks (1, 2, 3, 10, 15, 16, 26, 31, 33, 40 = gemm8f, 50 = gemm_sm), plus 41 = gemm8p, 11 (160x128 with a
-  // 3-stage ring), 20 (gemm8s, the [256][32]-image 256x256 kernel gemm8f replaced in r05), 21 (8-wave 256x128) and
-  // 22 (the unstaggered gemm8 at 256x256) as A/B baselines (tests/diagnostics/gemm_bench.py); the sweep also covered
-  // 128x192, 192x128, 128x160, 160x160, 224x128, 96x192, 64x128, 160x192, 192x192, 256x128 on 4 waves and 128x256 /
-  // 128x128 on 8 waves (slower on every MaPLe shape); r05 (profiles/r05_v2..v4_*): 224x96 / 224x128 / 208x96 4-wave
-  // one-round tiles, 8-wave full-line 160x128 / 192x128 / 128x128 / 96x192 (gemm8g) and a persistent gemm8f whose next
-  // tile's loads precede the current tile's buffer-store epilogue (gemm8fp) -- none faster where it would be picked
-  // (gemm8g 192x128 within +0..2 % on the c4 K >= 2 304 products; gemm8fp +3..+11 % on some C5 products and -4..-60 %
-  // on others), removed
+  // tile ids: 1 128x128, 2 128x64, 3 64x64, 10 160x128, 15 96x128, 16 160x64, 26 96x64, 31 64x64 and 33 32x64 with a
+  // 4-stage ring, 40 256x256 on 8 waves (gemm8f; K = 64 runs on 128x128), 50 gemm_sm: the heuristic picks every one;
+  // 20 gemm8s, the A/B baseline of gemm8f.  The unstaggered 8-wave ancestor, the persistent variant of gemm8f, a
+  // 3-stage 160x128 ring and the other tile shapes of the sweeps were measured and removed.
   switch (tile) {
     case 1: return launch_tile<128, 128, 2, 2, 2>(a, epilogue, st);
     case 2: return launch_tile<128, 64, 2, 2, 2>(a, epilogue, st);
     case 3: return launch_tile<64, 64, 2, 2, 2>(a, epilogue, st);
     case 10: return launch_tile<160, 128, 2, 2, 2>(a, epilogue, st);
-    case 11: return launch_tile<160, 128, 2, 2, 3>(a, epilogue, st);
     case 15: return launch_tile<96, 128, 2, 2, 2>(a, epilogue, st);
     case 16: return launch_tile<160, 64, 2, 2, 2>(a, epilogue, st);
     case 26: return launch_tile<96, 64, 2, 2, 2>(a, epilogue, st);
     case 31: return launch_tile<64, 64, 2, 2, 4>(a, epilogue, st);
     case 33: return launch_tile<32, 64, 2, 2, 4>(a, epilogue, st);
     case 20: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8s(a, epilogue, st);
-    case 21: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8<256, 128, 2, 4>(a, epilogue, st);
-    case 22: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8<256, 256, 2, 4>(a, epilogue, st);
     case 40: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8f(a, epilogue, st);
-    case 41: return K < 128 ? launch_tile<128, 128, 2, 2, 2>(a, epilogue, st) : launch_tile8p(a, epilogue, st);
     case 50: return launch_small_m(a, epilogue, st);
     default: return mf_set_error("mf_gemm: bad tile id", -2);
   }

@@ -17,16 +17,17 @@
 int main(int argc, char** argv) {
   int M = argc > 1 ? atoi(argv[1]) : 6368, N = argc > 2 ? atoi(argv[2]) : 2304, K = argc > 3 ? atoi(argv[3]) : 768;
   int epi = argc > 4 ? atoi(argv[4]) : 1, tile = argc > 5 ? atoi(argv[5]) : 1;
+  const bool aux_out = argc > 6 ? atoi(argv[6]) != 0 : true;
+  // the tile's BM x BN, as in mf_gemm's switch (an explicit tile id of a row-major product; 20 / 40 at K = 64 run 128x128)
   int BM = 128, BN = 128;
   if (tile == 2) BN = 64;
-  if (tile == 3) BM = BN = 64;
-  if (tile >= 20) { BM = tile == 23 || tile == 24 ? 128 : 256; BN = (tile == 20 || tile == 23 || tile >= 27) ? 256 : 128; }
-  const bool aux_out = argc > 6 ? atoi(argv[6]) != 0 : true;
-  // tile 27 (persistent): one stamp row per TILE (start = its loop iteration), not per workgroup
+  if (tile == 3 || tile == 31) BM = BN = 64;
   if (tile == 10) { BM = 160; BN = 128; }
   if (tile == 15) { BM = 96; BN = 128; }
   if (tile == 16) { BM = 160; BN = 64; }
   if (tile == 26) { BM = 96; BN = 64; }
+  if (tile == 33) { BM = 32; BN = 64; }
+  if ((tile == 20 || tile == 40) && K >= 128) BM = BN = 256;
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   _Float16 *A, *B, *C, *bias, *aux;
   hipMalloc(&A, (size_t)M * K * 2); hipMalloc(&B, (size_t)N * K * 2); hipMalloc(&C, (size_t)M * N * 2);

@@ -13,7 +13,7 @@ from collections import defaultdict
 
 # (kernel, workgroups) -> (product, M, N, K, aux_read) at c4 (vision M = 6368, text M = 2926)
 C4 = {
-    ("gemm8s_kernel<1>", 225): ("vision in_proj fwd", 6368, 2304, 768, False),
+    ("gemm8f_kernel<1>", 225): ("vision in_proj fwd", 6368, 2304, 768, False),
     ("gemm_nt_kernel<160,128,2,2,2,3,false,false>", 960): ("vision c_fc fwd (+QuickGELU, pre-activation out)", 6368, 3072, 768, False),
     ("gemm_nt_kernel<96,128,2,2,2,2,false,false>", 402): ("vision c_proj fwd / c_fc dX (+residual)", 6368, 768, 3072, True),
     ("gemm_nt_kernel<160,64,2,2,2,2,false,false>", 480): ("vision out_proj fwd (+residual)", 6368, 768, 768, True),

@@ -31,72 +31,66 @@ def assert_ulps(out, ref, max_ulp=1.0, frac=1e-2, what="", floor=2e-5):
     assert bad <= frac, f"{what}: {bad:.4f} of elements beyond half an ulp"
 
 
-@pytest.mark.parametrize("M,N,K", [(6368, 2304, 768), (513, 700, 256), (300, 516, 128)])
-def test_gemm8_staggered_matches_unstaggered(dev, M, N, K):
-    """The ping-pong 256x256 kernel (tile 20) issues every accumulator's MFMAs in the same k order as
-    the unstaggered one (tile 22): outputs bit-identical."""
-    g = torch.Generator(device="cpu").manual_seed(M * 7 + K)
-    A = torch.randn(M, K, generator=g).half().to(dev)
-    B = (torch.randn(N, K, generator=g) * K ** -0.5).half().to(dev)
-    b = (torch.randn(N, generator=g) * 0.1).half().to(dev)
-    C20 = ops.gemm_nt(A, B, bias=b, epilogue=ops.EPI_BIAS, tile=20)
-    C22 = ops.gemm_nt(A, B, bias=b, epilogue=ops.EPI_BIAS, tile=22)
-    assert torch.equal(C20, C22)
+_FP16_EPIS = (ops.EPI_NONE, ops.EPI_BIAS, ops.EPI_BIAS_RESID, ops.EPI_BIAS_GELU, ops.EPI_DGELU, ops.EPI_RESID)
+_8WAVE_SHAPES = [(33000, 1024, 192), (77000, 2048, 512), (20001, 512, 128), (30000, 760, 128), (20001, 2304, 768),
+                 (1000, 256, 192), (6368, 2304, 768)]
 
 
-@pytest.mark.parametrize("M,N,K", [(33000, 1024, 192), (77000, 2048, 512), (20001, 512, 128), (30000, 760, 128),
-                                   (20001, 2304, 768), (1000, 256, 192), (6368, 2304, 768)])
-def test_gemm8_fullline_matches_staggered(dev, M, N, K):
-    """The full-line 256x256 kernel gemm8f (tile 40: [128 rows][64 k] half-tiles) against gemm8s (tile 20: [256
-    rows][32 k]) -- bit-identical for every fp16 epilogue, ragged M / N included, and the pre-activation store
-    skipped (aux_out null, the forward-only engine) without changing C."""
+def _assert_tiles_bit_identical(dev, M, N, K, tiles, epis):
+    """Every epilogue in `epis` gives the same bits on every tile id in `tiles` (C, and the pre-activation of
+    EPI_BIAS_GELU), and EPI_BIAS_GELU without the pre-activation store (aux_out null, the forward-only engine) gives
+    the same C."""
     g = torch.Generator(device="cpu").manual_seed(M + K)
     A = torch.randn(M, K, generator=g).half().to(dev)
     B = (torch.randn(N, K, generator=g) * K ** -0.5).half().to(dev)
     b = (torch.randn(N, generator=g) * 0.1).half().to(dev)
     R = torch.randn(M, N, generator=g).half().to(dev)
-    for epi in (ops.EPI_NONE, ops.EPI_BIAS, ops.EPI_BIAS_RESID, ops.EPI_BIAS_GELU, ops.EPI_DGELU, ops.EPI_RESID):
+    for epi in epis:
         kw = {"bias": b} if epi in (ops.EPI_BIAS, ops.EPI_BIAS_RESID, ops.EPI_BIAS_GELU) else {}
         outs = []
-        for tile in (20, 40):
+        for tile in tiles:
             aux_out = torch.empty(M, N, device=dev, dtype=torch.float16) if epi == ops.EPI_BIAS_GELU else None
             aux_in = R if epi in (ops.EPI_BIAS_RESID, ops.EPI_DGELU, ops.EPI_RESID) else None
             C = ops.gemm_nt(A, B, aux_in=aux_in, aux_out=aux_out, epilogue=epi, tile=tile, **kw)
             outs.append((C, aux_out))
         if epi == ops.EPI_BIAS_GELU:  # the forward-only engine's form: no pre-activation store
-            for tile in (20, 40):
+            for tile in tiles:
                 outs.append((ops.gemm_nt(A, B, epilogue=epi, tile=tile, **kw), None))
         torch.cuda.synchronize()
+        assert outs[0][0].dtype == (torch.float32 if epi == ops.EPI_F32 else torch.float16)
         for k, (C, aux_out) in enumerate(outs[1:], 1):
             assert torch.equal(outs[0][0], C), f"epilogue {epi}, variant {k}"
             if aux_out is not None:
                 assert torch.equal(outs[0][1], aux_out), f"epilogue {epi}, variant {k} (pre-activation)"
 
 
-@pytest.mark.parametrize("M,N,K", [(79600, 2304, 768), (19900, 768, 3072), (3000, 512, 128), (77000, 512, 512)])
-def test_gemm8p_persistent_matches_gemm8f(dev, M, N, K):
-    """The persistent 256x256 kernel gemm8p (tile 41: one workgroup per CU walking its XCD's tiles, the next tile's
-    prologue under this tile's register-direct epilogue) against gemm8f (tile 40) -- bit-identical for every fp16
-    epilogue, ragged M included, with and without the pre-activation store."""
-    g = torch.Generator(device="cpu").manual_seed(M + K + 1)
-    A = torch.randn(M, K, generator=g).half().to(dev)
-    B = (torch.randn(N, K, generator=g) * K ** -0.5).half().to(dev)
-    b = (torch.randn(N, generator=g) * 0.1).half().to(dev)
-    R = torch.randn(M, N, generator=g).half().to(dev)
-    for epi in (ops.EPI_NONE, ops.EPI_BIAS, ops.EPI_BIAS_RESID, ops.EPI_BIAS_GELU, ops.EPI_DGELU, ops.EPI_RESID):
-        kw = {"bias": b} if epi in (ops.EPI_BIAS, ops.EPI_BIAS_RESID, ops.EPI_BIAS_GELU) else {}
-        aux_in = R if epi in (ops.EPI_BIAS_RESID, ops.EPI_DGELU, ops.EPI_RESID) else None
-        for with_aux_out in ((True, False) if epi == ops.EPI_BIAS_GELU else (False,)):
-            outs = []
-            for tile in (40, 41):
-                aux_out = torch.full((M, N), 3.0, device=dev, dtype=torch.float16) if with_aux_out else None
-                C = torch.full((M, N), 5.0, device=dev, dtype=torch.float16)
-                ops.gemm_nt(A, B, C=C, aux_in=aux_in, aux_out=aux_out, epilogue=epi, tile=tile, **kw)
-                outs.append((C, aux_out))
-            torch.cuda.synchronize()
-            assert torch.equal(outs[0][0], outs[1][0]), f"epilogue {epi}, aux_out {with_aux_out}"
-            if with_aux_out:
-                assert torch.equal(outs[0][1], outs[1][1]), f"epilogue {epi} (pre-activation)"
+@pytest.mark.parametrize("M,N,K", _8WAVE_SHAPES)
+def test_gemm8_fullline_matches_staggered(dev, M, N, K):
+    """The full-line 256x256 kernel gemm8f (tile 40: [128 rows][64 k] half-tiles) against gemm8s (tile 20: [256
+    rows][32 k]) -- bit-identical for every fp16 epilogue, ragged M / N included, and the pre-activation store
+    skipped (aux_out null, the forward-only engine) without changing C."""
+    _assert_tiles_bit_identical(dev, M, N, K, (20, 40), _FP16_EPIS)
+
+
+@pytest.mark.parametrize("M,N,K", _8WAVE_SHAPES + [(513, 2304, 128)])
+def test_gemm8f_matches_4wave_tile(dev, M, N, K):
+    """The 8-wave 256x256 kernel gemm8f (tile 40) against the 4-wave 128x128 tile (tile 1): both sum every output as
+    one MFMA chain from a zero accumulator over k ascending in 32-deep steps, with the same operand order and k-to-lane
+    mapping, and share the epilogue -- bit-identical for the fp32 accumulators (EPI_F32) and every fp16 epilogue,
+    ragged M / N included, with and without the pre-activation store.  (513, 2304, 128): 27 tiles, the XCD blocking
+    at 8 N-ranges (xb = 3)."""
+    _assert_tiles_bit_identical(dev, M, N, K, (1, 40), _FP16_EPIS + (ops.EPI_F32,))
+
+
+@pytest.mark.parametrize("tile", [11, 21, 22, 41])
+def test_gemm_removed_tile_ids_raise(dev, tile):
+    """The ids of the removed kernels (the 3-stage 160x128 ring, the unstaggered 8-wave gemm8 and the persistent
+    variant of gemm8f) are bad tile ids."""
+    from federated_multi_modal_amd._lib import MapfedError
+    A = torch.randn(64, 128).half().to(dev)
+    B = torch.randn(64, 128).half().to(dev)
+    with pytest.raises(MapfedError):
+        ops.gemm_nt(A, B, tile=tile)
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(2926, 512, 2048, 2), (2926, 1536, 512, 1), (6368, 768, 3072, 0),
@@ -125,23 +119,24 @@ def test_gemm_side_tower_tile_hint_is_bit_identical(dev, M, N, K, epi):
 
 @pytest.mark.parametrize("M,N,K,tile", [(796, 2304, 768, 0), (6368, 768, 3072, 0), (770, 512, 2048, 1),
                                         (130, 44, 64, 3), (257, 1536, 512, 2), (6368, 3072, 768, 0),
-                                        # 8-wave phase-pipelined family (tiles 20 = staggered 256x256, 21,
-                                        # 22 = unstaggered 256x256), ragged M / N, K down to two K-tiles
-                                        (6368, 2304, 768, 20), (1000, 760, 192, 20), (6368, 3072, 768, 21),
-                                        (300, 388, 64, 21), (777, 132, 128, 21), (129, 260, 320, 20),
-                                        (300, 516, 128, 20), (6368, 2304, 768, 22), (129, 260, 320, 22),
-                                        # 160x128 (tiles 10, 11)
-                                        (6368, 768, 3072, 10), (333, 136, 128, 10), (6368, 768, 2304, 11),
-                                        (170, 260, 192, 11),
+                                        # the staggered 8-wave 256x256 tile with [256][32] images (gemm8s, 20),
+                                        # ragged M / N, K down to two K-tiles
+                                        (6368, 2304, 768, 20), (1000, 760, 192, 20), (129, 260, 320, 20),
+                                        (300, 516, 128, 20),
+                                        # 160x128 (tile 10)
+                                        (6368, 768, 3072, 10), (333, 136, 128, 10), (6368, 768, 2304, 10),
+                                        (170, 260, 192, 10),
                                         # 96x128, 160x64, 96x64 (tiles 15, 16, 26) as chosen by the heuristic
                                         (6368, 768, 3072, 0), (6368, 768, 768, 0), (2926, 1536, 512, 0),
                                         (97, 200, 64, 15), (161, 72, 128, 16), (100, 76, 192, 26),
                                         # the small clients' 4-stage rings (tiles 31, 33)
                                         (796, 768, 3072, 31), (770, 512, 2048, 33), (100, 72, 320, 31),
                                         (33, 136, 192, 33),
-                                        # the full-line 8-wave 256x256 tile (gemm8f, 40)
+                                        # the 8-wave 256x256 tile (gemm8f, 40), ragged M / N, K down to two K-tiles
+                                        # (K = 64 runs on 128x128)
                                         (6368, 2304, 768, 40), (1000, 760, 192, 40), (129, 260, 128, 40),
-                                        (20001, 2304, 768, 40), (300, 516, 192, 40)])
+                                        (20001, 2304, 768, 40), (300, 516, 192, 40), (129, 260, 320, 40),
+                                        (300, 516, 128, 40), (777, 132, 128, 40)])
 def test_gemm_bias(dev, M, N, K, tile):
     g = torch.Generator(device="cpu").manual_seed(M + N + K)
     A = torch.randn(M, K, generator=g).half().to(dev)
@@ -229,7 +224,7 @@ def _gelu16(f):
     return (f.float() * t2.float()).half()
 
 
-@pytest.mark.parametrize("tile", [0, 10, 15, 20, 21])
+@pytest.mark.parametrize("tile", [0, 10, 15, 20, 40])
 def test_gemm_epilogues(dev, tile):
     torch.manual_seed(0)
     M, N, K = 600, 1024, 256
