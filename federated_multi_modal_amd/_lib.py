@@ -67,6 +67,8 @@ SIGNATURES = {
     "mf_fedopt_step": [P, I, I, F, F, F, F, P, P, P, P, L, P, L, P, P, P],
     "mf_fedopt_deliver": [P, P, L, P, L, P, P, P],
     "mf_fedavg_reduce_ordered": [P, I, L, L, P, P],
+    "mf_fedavg_reduce_trimmed": [P, I, L, L, I, L, P, P],
+    "mf_fedavg_pack_robust": [P, L, P, L, P, P, P],
     "mf_seq_grow": [P, P, P, P, I, I, I, I, I, P],
     "mf_seq_grow_bwd": [P, P, I, I, I, I, I, P],
     "mf_seq_scatter": [P, L, P, L, I, I, I, I, P],

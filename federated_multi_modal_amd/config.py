@@ -221,6 +221,11 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # "fedadam", "fedyogi" (Reddi et al.); eta, beta1, beta2 and tau of those papers
                            SERVER_OPT="none", SERVER_LR=1.0, SERVER_MOMENTUM=0.9, SERVER_BETA2=0.99,
                            SERVER_TAU=1e-3,
+                           # robust aggregation in the mean's place (Yin, Chen, Ramchandran, Bartlett: "Byzantine-
+                           # Robust Distributed Learning: Towards Optimal Statistical Rates", ICML 2018): "none",
+                           # "median" (coordinate-wise) or "trimmed_mean" (coordinate-wise, the TRIM_K smallest and
+                           # the TRIM_K largest of the clients' values dropped; 2 * TRIM_K < NUM_CLIENTS)
+                           ROBUST_AGG="none", TRIM_K=1,
                            # size of each client's synthetic test split (no DATASET.ROOT); 0: one test batch
                            SYNTHETIC_TEST_IMAGES=0,
                            # > 0: the synthetic splits repeat that many generated images (bench timing runs)

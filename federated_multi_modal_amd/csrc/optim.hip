@@ -12,6 +12,7 @@
 // total norm in fp32, coef = clamp(1/(total+1e-6), max 1); g = T(g*coef); d_p = T(g + wd*p);
 // buf = d_p (first step) or T(T(buf*mom) + d_p); p = T(p - lr*buf).
 #include <type_traits>
+#include <utility>
 
 #include "mf_common.h"
 
@@ -255,16 +256,19 @@ __global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f
 // Learning of Deep Networks from Decentralized Data", AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The
 // client's weight travels in its bucket: bucket[0:n] = w * float(p) (the fp32 product is formed and stored here; the
 // sum is formed by reduce_ordered_kernel, so no fused multiply-add spans the two), bucket[n] = w, bucket[n+1] = 1
-// (its vote).  An invalid client (maple_fed.py:272-277) writes zeros everywhere.
+// (its vote).  An invalid client (maple_fed.py:272-277) writes zeros everywhere -- or, ABSENT (the robust
+// aggregation's bucket: the weighted layout at w = 1, and 1.f * x is x), the quiet NaN reduce_trimmed_kernel reads as
+// "this client is absent", since a zero would take part in a median.
 template <bool WEIGHTED>
 constexpr int TAIL = WEIGHTED ? 2 : 1;
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool ABSENT = false>
 __global__ void pack_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32, int64_t n32,
                             const int* __restrict__ invalid, float* __restrict__ bucket, float w) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = n16 + n32;
   const bool bad = invalid && invalid[0] != 0;
+  const float none = ABSENT ? __int_as_float(0x7fc00000) : 0.f;
   const auto weigh = [&](float x) {
     if constexpr (WEIGHTED)
       return w * x;
@@ -272,13 +276,13 @@ __global__ void pack_kernel(const f16* __restrict__ p16, int64_t n16, const floa
       return x;
   };
   if (i < n16)
-    bucket[i] = bad ? 0.f : weigh((float)p16[i]);
+    bucket[i] = bad ? none : weigh((float)p16[i]);
   else if (i < n)
-    bucket[i] = bad ? 0.f : weigh(p32[i - n16]);
+    bucket[i] = bad ? none : weigh(p32[i - n16]);
   else if (i == n)
-    bucket[i] = bad ? 0.f : (WEIGHTED ? w : 1.f);
+    bucket[i] = bad ? none : (WEIGHTED ? w : 1.f);
   else if (WEIGHTED && i == n + 1)
-    bucket[i] = bad ? 0.f : 1.f;
+    bucket[i] = bad ? none : 1.f;
 }
 
 // fp16 `val` to element i of [fp16 trainables | fp32 trainables] and of the global copy (g16 / g32 may be null)
@@ -488,6 +492,144 @@ __global__ void reduce_ordered_kernel(const float* __restrict__ g, int nclients,
       out[j] = acc;
     }
   }
+}
+
+// Robust aggregation: the coordinate-wise median and beta-trimmed mean of Yin, Chen, Ramchandran, Bartlett
+// ("Byzantine-Robust Distributed Learning: Towards Optimal Statistical Rates", ICML 2018) over the same
+// [client][coordinate] image reduce_ordered_kernel sums.  Per coordinate (the contract of include/mapfed.h): a NaN is
+// an absent client, the m present values are sorted in the IEEE total order, k = min(trim_k, (m - 1) / 2) are cut at
+// either end, and the kept ones are summed in ascending order (one fp32 add each, starting from the first kept value)
+// and divided by m - 2k.  A sum in sorted order depends on neither the client order nor the layout of the exchange.
+//
+// An absent client, and the padding of the client count to the network's size:
+constexpr unsigned QUIET_NAN = 0x7fc00000u;
+
+// the total order as a signed integer compare (an involution: the same expression turns a key back into its bits)
+MF_DEV int order_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+// Batcher's odd-even merge sort on NP = 2^q keys as a list of compare-exchange pairs, built at compile time
+// (NP = 8: 19 pairs, 64: 543), so the network below unrolls into min / max pairs on named registers: an index that is
+// not a compile-time constant would send the key array to scratch.
+template <int NP>
+struct SortNet {
+  int a[NP * 10], b[NP * 10], count;
+};
+
+template <int NP>
+constexpr SortNet<NP> make_sort_net() {
+  SortNet<NP> s{};
+  for (int p = 1; p < NP; p *= 2)
+    for (int k = p; k >= 1; k /= 2)
+      for (int j = k % p; j + k < NP; j += 2 * k)
+        for (int i = 0; i < k && i + j + k < NP; ++i)
+          if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+            s.a[s.count] = i + j;
+            s.b[s.count] = i + j + k;
+            ++s.count;
+          }
+  return s;
+}
+
+template <int NP>
+struct SortNetOf {
+  static constexpr SortNet<NP> net = make_sort_net<NP>();
+};
+
+template <int A, int B, int NP>
+MF_DEV void compare_exchange(unsigned (&key)[NP]) {
+  const unsigned lo = min(key[A], key[B]), hi = max(key[A], key[B]);
+  key[A] = lo;
+  key[B] = hi;
+}
+
+template <int NP, size_t... T>
+MF_DEV void sort_keys(unsigned (&key)[NP], std::index_sequence<T...>) {
+  (compare_exchange<SortNetOf<NP>::net.a[T], SortNetOf<NP>::net.b[T]>(key), ...);
+}
+
+// one coordinate: key[] holds the NP raw bit patterns (the padding as NaNs) and is consumed.  The sort runs on
+// u = order_key(bits) - order_key(-Inf) as an unsigned number: the present values keep their order in
+// [0, U_INF], and every NaN, whatever its sign, wraps to above U_INF, so absent clients sort to the top untouched.
+constexpr unsigned KEY_NINF = 0x807fffffu;         // order_key(bits of -Inf)
+constexpr unsigned U_INF = 0x7f800000u - KEY_NINF;  // u of +Inf, the largest present value
+
+template <int NP>
+MF_DEV float trimmed_stat(unsigned (&key)[NP], int trim_k, bool is_count) {
+  int m = 0;
+#pragma unroll
+  for (int c = 0; c < NP; ++c) {
+    key[c] = (unsigned)order_key((int)key[c]) - KEY_NINF;
+    m += key[c] <= U_INF;
+  }
+  sort_keys<NP>(key, std::make_index_sequence<SortNetOf<NP>::net.count>{});
+  // the present values now stand at [0, m); the kept range is [k, m - k).  A position outside it adds -0.f, the
+  // identity of the fp32 add for every value (-0 included), and the accumulator starts as -0.f, so the sum is
+  // s_k, then one add per further kept value: it starts from the first kept value, not from +0.
+  const int k = m > 0 ? min(trim_k, (m - 1) >> 1) : 0;
+  const unsigned kept = (unsigned)(m - 2 * k);
+  float acc = -0.f;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const float v = __int_as_float(order_key((int)(key[p] + KEY_NINF)));
+    acc += (unsigned)(p - k) < kept ? v : -0.f;
+  }
+  if (is_count) return (float)m;
+  return m > 0 ? acc / (float)kept : 0.f;
+}
+
+// Each thread owns VEC whole coordinates i .. i + VEC - 1 < n (the launcher sees to that): VEC = 4 with one 16-byte
+// load per client, which needs stride % 4 == 0 and 16-byte aligned gathered / out, VEC = 1 with 4-byte loads; both
+// are contiguous across the wave, and both run the same arithmetic per coordinate.
+template <int NP, int VEC>
+__global__ void __launch_bounds__(256)
+    reduce_trimmed_kernel(const float* __restrict__ g, int nclients, int64_t stride, int64_t n, int trim_k,
+                          int64_t count_pos, float* __restrict__ out) {
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (i >= n) return;
+  if constexpr (VEC == 4) {
+    unsigned k0[NP], k1[NP], k2[NP], k3[NP];
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+      k0[c] = k1[c] = k2[c] = k3[c] = QUIET_NAN;
+      if (c < nclients) {
+        const float4 v = *(const float4*)(g + (int64_t)c * stride + i);
+        k0[c] = __float_as_uint(v.x);
+        k1[c] = __float_as_uint(v.y);
+        k2[c] = __float_as_uint(v.z);
+        k3[c] = __float_as_uint(v.w);
+      }
+    }
+    float4 r;
+    r.x = trimmed_stat<NP>(k0, trim_k, count_pos == i);
+    r.y = trimmed_stat<NP>(k1, trim_k, count_pos == i + 1);
+    r.z = trimmed_stat<NP>(k2, trim_k, count_pos == i + 2);
+    r.w = trimmed_stat<NP>(k3, trim_k, count_pos == i + 3);
+    *(float4*)(out + i) = r;
+  } else {
+    unsigned key[NP];
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+      key[c] = QUIET_NAN;
+      if (c < nclients) key[c] = __float_as_uint(g[(int64_t)c * stride + i]);
+    }
+    out[i] = trimmed_stat<NP>(key, trim_k, count_pos == i);
+  }
+}
+
+// Up to 16 clients: four coordinates per thread over the multiple-of-4 part when the image allows 16-byte loads
+// (4 * NP key registers), and the ragged tail, an unaligned image and 17 to 64 clients one coordinate per thread.
+template <int NP>
+void launch_reduce_trimmed(const float* g, int nclients, int64_t stride, int64_t n, int trim_k, int64_t count_pos,
+                           float* out, hipStream_t st) {
+  int64_t n4 = 0;
+  if constexpr (NP <= 16) {
+    if (stride % 4 == 0 && aligned(g, 16) && aligned(out, 16)) n4 = n & ~(int64_t)3;
+    if (n4 > 0)
+      reduce_trimmed_kernel<NP, 4><<<nblk(n4 / 4), 256, 0, st>>>(g, nclients, stride, n4, trim_k, count_pos, out);
+  }
+  if (n > n4)
+    reduce_trimmed_kernel<NP, 1><<<nblk(n - n4), 256, 0, st>>>(g + n4, nclients, stride, n - n4, trim_k,
+                                                              count_pos - n4, out + n4);
 }
 
 // flag[0] |= 1 if any element is NaN/Inf
@@ -702,6 +844,42 @@ extern "C" int mf_fedavg_reduce_ordered(const float* gathered, int nclients, int
   if (nclients < 1 || n < 0 || stride < n) return mf_set_error("mf_fedavg_reduce_ordered: bad sizes", -1);
   if (n == 0) return 0;
   reduce_ordered_kernel<<<nblk((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(gathered, nclients, stride, n, out);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// The robust aggregation's reduce in mf_fedavg_reduce_ordered's place (same image); median = a large trim_k
+extern "C" int mf_fedavg_reduce_trimmed(const float* gathered, int nclients, int64_t stride, int64_t n, int trim_k,
+                                        int64_t count_pos, float* out, void* stream) {
+  if (nclients < 1 || nclients > 64) return mf_set_error("mf_fedavg_reduce_trimmed: nclients not in [1, 64]", -1);
+  if (trim_k < 0) return mf_set_error("mf_fedavg_reduce_trimmed: trim_k < 0", -1);
+  if (n < 0 || stride < n) return mf_set_error("mf_fedavg_reduce_trimmed: bad sizes (n < 0 or stride < n)", -1);
+  if (count_pos >= n) return mf_set_error("mf_fedavg_reduce_trimmed: count_pos >= n", -1);
+  if (n == 0) return 0;
+  if (!gathered || !out) return mf_set_error("mf_fedavg_reduce_trimmed: null pointer", -1);
+  hipStream_t st = (hipStream_t)stream;
+  if (nclients <= 2)
+    launch_reduce_trimmed<2>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  else if (nclients <= 4)
+    launch_reduce_trimmed<4>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  else if (nclients <= 8)
+    launch_reduce_trimmed<8>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  else if (nclients <= 16)
+    launch_reduce_trimmed<16>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  else if (nclients <= 32)
+    launch_reduce_trimmed<32>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  else
+    launch_reduce_trimmed<64>(gathered, nclients, stride, n, trim_k, count_pos, out, st);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// The robust aggregation's bucket: mf_fedavg_pack_weighted's layout at weight 1, an invalid client all quiet NaNs
+extern "C" int mf_fedavg_pack_robust(const void* p16, int64_t n16, const float* p32, int64_t n32,
+                                     const int* invalid_flag, float* bucket, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack_robust: negative size", -1);
+  pack_kernel<true, true><<<nblk(n16 + n32 + TAIL<true>), 256, 0, (hipStream_t)stream>>>(
+      (const f16*)p16, n16, p32, n32, invalid_flag, bucket, 1.f);
   MF_CHECK_LAUNCH();
   return 0;
 }

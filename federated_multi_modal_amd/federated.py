@@ -60,6 +60,23 @@ applies the step to the same total (each holds the whole summed bucket after eit
 size 1) with the same kernel, so the replicated states stay bit-identical across the ranks without a further
 collective.  A round without a valid client leaves x, m, v untouched.  An x outside the fp16 range is delivered as
 +-inf, and the next round's validity scan then excludes every client.
+
+Robust aggregation (FED.ROBUST_AGG, off by default): the coordinate-wise median and the coordinate-wise trimmed mean
+of Yin, Chen, Ramchandran and Bartlett (ICML 2018), so that one client returning finite but wrong weights (a diverged
+local run, a corrupted shard) cannot move a global weight further than the honest clients' values reach.  A bucket
+built with robust="median" | "trimmed_mean" packs the weighted layout at weight 1, [trainables | 1 | 1], and an invalid
+client packs NaNs -- "absent" -- instead of zeros (mf_fedavg_pack_robust).  The "ordered" exchange is unchanged: rank r
+still receives shard r of every client's bucket in client order, which is exactly what a per-coordinate order
+statistic needs, and mf_fedavg_reduce_trimmed runs where mf_fedavg_reduce_ordered does: per coordinate it sorts the
+present values, drops trim_k at either end (as many as leave something; the median is a trim nobody reaches), sums
+the rest in ascending order and divides by their number.  At the vote element it writes the number of present
+clients instead, so the reduced bucket reads [statistic | 1 | n_valid] and the weighted unpack, the server step and
+n_valid() consume it as they are; with a server optimizer the statistic is the pseudo-gradient's target.  A sum in
+sorted order depends on neither the client order, the world size nor the clients per rank, so the fp32 statistic
+equals a single-process restatement bit for bit at any layout (tests/test_fedavg_robust_dist.py).  One process runs
+the same kernel over its buckets staged contiguously, also for a single client: it is what turns the absence marks
+into a zero vote.  Not combined with "allreduce" (a sum has lost the per-client values) or with client weights (a
+weighted median is another statistic).
 """
 from __future__ import annotations
 
@@ -72,6 +89,26 @@ import torch.distributed as dist
 from . import ops
 
 MODES = ("ordered", "allreduce")
+ROBUST = ("median", "trimmed_mean")
+MEDIAN_TRIM = ops.MEDIAN_TRIM  # a trim no client count reaches: the trimmed reduce degrades it to the median
+
+
+def robust_trim(robust: Optional[str], trim_k: int, mode: str = "ordered", weighted: bool = False) -> Optional[int]:
+    """The trim the reduce kernel is called with (None: no robust aggregation).  ValueError for an unknown name,
+    the "allreduce" mode, client weights, or trim_k < 1 for "trimmed_mean"."""
+    if robust is None:
+        return None
+    if robust not in ROBUST:
+        raise ValueError(f"robust aggregation {robust!r}: None or one of {ROBUST}")
+    if mode != "ordered":
+        raise ValueError(f'robust aggregation needs mode "ordered" (got {mode!r}): a sum has lost the per-client values')
+    if weighted:
+        raise ValueError("robust aggregation with a client weight: a weighted median is a different statistic")
+    if robust == "median":
+        return MEDIAN_TRIM
+    if isinstance(trim_k, bool) or not isinstance(trim_k, int) or not 1 <= trim_k <= MEDIAN_TRIM:
+        raise ValueError(f"trimmed_mean trim_k {trim_k!r}: an integer >= 1")
+    return trim_k
 
 
 class FederatedAbort(RuntimeError):
@@ -88,6 +125,8 @@ class _HipKernels:
     fedavg_reduce_ordered = staticmethod(ops.fedavg_reduce_ordered)
     fedopt_step = staticmethod(ops.fedopt_step)
     fedopt_deliver = staticmethod(ops.fedopt_deliver)
+    fedavg_pack_robust = staticmethod(ops.fedavg_pack_robust)
+    fedavg_reduce_trimmed = staticmethod(ops.fedavg_reduce_trimmed)
 
 
 SERVER_OPTS = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
@@ -209,7 +248,8 @@ class FedAvgBucket:
     """One client's bucket.  `engine` needs: device, n16, n32, flat16 (fp16 trainables), flat32 (fp32
     trainables) and after_weights_loaded().  `kernels` defaults to the HIP kernels; tests substitute host
     restatements to exercise the collective protocol on CPU ranks (gloo).  `weight` (finite, > 0) selects the
-    sample-weighted layout and kernels (module docstring); None is the reference's plain mean.
+    sample-weighted layout and kernels (module docstring); None is the reference's plain mean.  `robust`
+    ("median" | "trimmed_mean", with `trim_k` values cut at either end) selects the robust aggregation instead.
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
@@ -217,9 +257,11 @@ class FedAvgBucket:
 
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None, kernels=_HipKernels,
                  mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None,
-                 server: Optional["ServerOptimizer"] = None):
+                 server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
+        self.trim = robust_trim(robust, trim_k, mode, weight is not None)
+        self.robust, self.trim_k = robust, trim_k
         if weight is not None:
             weight = float(weight)
             if not math.isfinite(weight) or weight <= 0.0:
@@ -236,8 +278,10 @@ class FedAvgBucket:
         # [bucket | count | zero padding to a multiple of the world size]: one contiguous buffer so the
         # mean and the valid-client count travel in the same collectives.  With a client weight (every client
         # of a run has one or none): [weight * bucket | weight | count | padding], so the weighted sum, the sum
-        # of the weights and the count travel together and the exchange itself is unchanged
-        tail = 1 if weight is None else 2
+        # of the weights and the count travel together and the exchange itself is unchanged.  The robust
+        # aggregation uses that layout at weight 1 ([bucket | 1 | count | padding])
+        self.weighted = weight is not None or robust is not None
+        tail = 2 if self.weighted else 1
         padded = -(-(n + tail) // self.world) * self.world
         self.pbuf = torch.zeros(padded, device=dev, dtype=torch.float32)
         self.buf = self.pbuf[:n + tail]
@@ -266,7 +310,9 @@ class FedAvgBucket:
             self.flag.zero_()
             self.k.nonfinite_flag(e.flat16, self.flag)
             self.k.nonfinite_flag(e.flat32, self.flag)
-        if self.weight is None:
+        if self.robust is not None:
+            self.k.fedavg_pack_robust(e.flat16, e.flat32, self.flag, self.buf)
+        elif self.weight is None:
             self.k.fedavg_pack(e.flat16, e.flat32, self.flag, self.buf)
         else:
             self.k.fedavg_pack_weighted(e.flat16, e.flat32, self.flag, self.weight, self.buf)
@@ -283,12 +329,12 @@ class FedAvgBucket:
         sv = self.server
         if sv is not None:
             if sv.pending:
-                self.k.fedopt_step(self.buf, self.weight is not None, sv.name, sv.beta1, sv.beta2, sv.tau, sv.lr,
+                self.k.fedopt_step(self.buf, self.weighted, sv.name, sv.beta1, sv.beta2, sv.tau, sv.lr,
                                    sv.x, sv.m, sv.v, e.flat16, e.flat32, self.global16, self.global32)
                 sv.pending = False
             else:
                 self.k.fedopt_deliver(sv.x, e.flat16, e.flat32, self.global16, self.global32)
-        elif self.weight is None:
+        elif not self.weighted:
             self.k.fedavg_unpack(self.buf, e.flat16, e.flat32, self.global16, self.global32)
         else:
             self.k.fedavg_unpack_weighted(self.buf, e.flat16, e.flat32, self.global16, self.global32)
@@ -310,7 +356,8 @@ class FedAvgBucket:
     @property
     def exchange(self) -> "FedAvgExchange":
         if self._x is None:
-            self._x = FedAvgExchange([self], group=self.group, mode=self.mode, shard_single=self.shard_single)
+            self._x = FedAvgExchange([self], group=self.group, mode=self.mode, shard_single=self.shard_single,
+                                     robust=self.robust, trim_k=self.trim_k)
         return self._x
 
     @property
@@ -345,13 +392,15 @@ class FedAvgExchange:
     """The exchange of one rank's buckets (its C clients, in client order) with every other rank's."""
 
     def __init__(self, buckets: Sequence[FedAvgBucket], group: Optional[dist.ProcessGroup] = None,
-                 mode: str = "ordered", shard_single: bool = False):
+                 mode: str = "ordered", shard_single: bool = False, robust: Optional[str] = None, trim_k: int = 1):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         self.b = list(buckets)
         assert self.b and len({x.pbuf.numel() for x in self.b}) == 1
         # one layout per exchange: every bucket weighted (n + 2 floats) or none (n + 1)
         assert len({x.weight is None for x in self.b}) == 1, "weighted and unweighted buckets in one exchange"
+        self.trim = robust_trim(robust, trim_k, mode, self.b[0].weight is not None)
+        assert all(x.trim == self.trim for x in self.b), "the buckets and their exchange differ in robust / trim_k"
         b0 = self.b[0]
         self.group, self.mode, self.k = group, mode, b0.k
         self.C = len(self.b)
@@ -379,6 +428,11 @@ class FedAvgExchange:
             self.host_stage = dev.type == "cuda" and dist.get_backend(group) != "nccl"
             if dev.type == "cuda" and not self.host_stage:
                 self.side = torch.cuda.Stream(device=dev)
+        # robust, one process: the rank's buckets staged [client][coordinate], the image the trimmed reduce reads
+        self.local_stage = None
+        if self.trim is not None and not self.distributed:
+            self.local_stage = torch.empty(self.C, padded, device=dev, dtype=torch.float32)
+        self.count_pos = b0.buf.numel() - 1  # the vote element, the last of the bucket
         self.started = False
         self.work = None
 
@@ -396,6 +450,14 @@ class FedAvgExchange:
         self.total.copy_(self.b[0].pbuf)
         for x in self.b[1:]:
             self.total.add_(x.pbuf)
+        return self.total
+
+    def _local_robust(self) -> torch.Tensor:
+        """The robust statistic over the rank's buckets (one process): the kernel of the sharded chain over the whole
+        bucket.  It runs for a single client too: it turns an invalid client's absence marks into a zero vote."""
+        for j, x in enumerate(self.b):
+            self.local_stage[j].copy_(x.pbuf)
+        self.k.fedavg_reduce_trimmed(self.local_stage.view(-1), self.C, self.trim, self.count_pos, self.total)
         return self.total
 
     def start(self):
@@ -420,7 +482,8 @@ class FedAvgExchange:
             self.work = self._ordered_chain(send)
 
     def _ordered_chain(self, send: torch.Tensor):
-        """all_to_all of the shards -> client-ordered sum of this rank's shard -> all_gather of the sums.
+        """all_to_all of the shards -> client-ordered sum (robust: the trimmed reduce) of this rank's shard ->
+        all_gather of the results.
         One code path for every backend: under RCCL (on the side stream) a2a.wait() is a stream dependency;
         under gloo it is a host wait, and with device buckets (host_stage) the collectives move host copies.
         Returns the all_gather's work handle (None when it completed here)."""
@@ -430,7 +493,12 @@ class FedAvgExchange:
         a2a.wait()
         if hs:
             self.recv.copy_(recv)
-        self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
+        if self.trim is None:
+            self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
+        else:  # the robust statistic of this rank's shard; the vote element, if it lies in this shard, counts
+            pos = self.count_pos - dist.get_rank(self.group) * self.S
+            self.k.fedavg_reduce_trimmed(self.recv, self.world * self.C, self.trim, pos if 0 <= pos < self.S else -1,
+                                         self.shard)
         if hs:
             out = torch.empty(self.total.numel(), dtype=torch.float32)
             dist.all_gather_into_tensor(out, self.shard.cpu(), group=self.group)
@@ -443,7 +511,10 @@ class FedAvgExchange:
             self.work.wait()
             self.work = None
         if not self.distributed:
-            self._local_sum()
+            if self.trim is None:
+                self._local_sum()
+            else:
+                self._local_robust()
         if self.total is not self.b[0].pbuf:
             for x in self.b:
                 x.pbuf.copy_(self.total)

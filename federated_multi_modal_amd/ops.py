@@ -849,5 +849,39 @@ def fedavg_reduce_ordered(gathered, nclients, out):
     call("mf_fedavg_reduce_ordered", _p(gathered), nclients, stride, out.numel(), _p(out), _s())
 
 
+MEDIAN_TRIM = 2 ** 31 - 1  # a trim no client count reaches: mf_fedavg_reduce_trimmed degrades it to the median
+
+
+def fedavg_reduce_trimmed(gathered, nclients, trim_k, count_pos, out):
+    """out = the coordinate-wise trim_k-trimmed mean (median: MEDIAN_TRIM) over gathered.view(nclients, -1)[:, :n],
+    n = out.numel(); a NaN is an absent client; out[count_pos] = the number of present ones (count_pos -1: none)
+    (mf_fedavg_reduce_trimmed)."""
+    nclients, trim_k, count_pos = int(nclients), int(trim_k), int(count_pos)
+    if not 1 <= nclients <= 64:
+        raise ValueError(f"nclients: 1 to 64 required, got {nclients}")
+    if not 0 <= trim_k <= MEDIAN_TRIM:
+        raise ValueError(f"trim_k: 0 to {MEDIAN_TRIM} required, got {trim_k}")
+    for name, t in (("gathered", gathered), ("out", out)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous fp32 required, got {t.dtype} {tuple(t.shape)}")
+    stride = gathered.numel() // nclients
+    if gathered.numel() != stride * nclients or out.numel() > stride:
+        raise ValueError(f"gathered: {nclients} rows of at least {out.numel()} floats required, got {gathered.numel()}")
+    if count_pos >= out.numel():
+        raise ValueError(f"count_pos: below {out.numel()} (or -1) required, got {count_pos}")
+    if _overlap(gathered, out):
+        raise ValueError("out: a buffer of its own required (it overlaps gathered)")
+    call("mf_fedavg_reduce_trimmed", _p(gathered), nclients, stride, out.numel(), trim_k, max(count_pos, -1), _p(out),
+         _s())
+
+
+def fedavg_pack_robust(p16, p32, invalid_flag, bucket):
+    """bucket: n16 + n32 + 2 floats = [trainables | 1 | 1], an invalid client all quiet NaNs (mf_fedavg_pack_robust)."""
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    _check_flat("bucket", bucket, torch.float32, p16.numel() + p32.numel() + 2)
+    call("mf_fedavg_pack_robust", _p(p16), p16.numel(), _p(p32), p32.numel(), _p(invalid_flag), _p(bucket), _s())
+
+
 def nonfinite_flag(x, flag):
     call("mf_nonfinite_flag", _p(x), x.numel(), int(x.dtype == torch.float16), _p(flag), _s())

@@ -34,7 +34,7 @@ import torch.distributed as dist
 from . import ops
 from .data import DATASET_CLASSES, SyntheticClientDataManager, unified_classnames
 from .engine import EngineConfig, MapleEngine
-from .federated import (SERVER_OPTS, FedAvgBucket, FedAvgExchange, FederatedAbort, ServerOptimizer,
+from .federated import (ROBUST, SERVER_OPTS, FedAvgBucket, FedAvgExchange, FederatedAbort, ServerOptimizer,
                         resolve_client_weights)
 from .captions import caption_tokens, draw_caption_weights, has_captions
 from .modules import CustomCLIP
@@ -620,16 +620,49 @@ class MaPLeFederated(TrainerX):
             print(line)
         return name, hp
 
+    def _robust_cfg(self, get):
+        """FED.ROBUST_AGG and FED.TRIM_K, validated: (None | "median" | "trimmed_mean", trim_k).  ValueError naming the
+        key for an unknown name, TRIM_K < 1, a trim that leaves no client, more than 64 clients, another exchange than
+        "ordered" or client weights."""
+        name = get("ROBUST_AGG", "none")
+        name = name.strip().lower() if isinstance(name, str) else name
+        if name != "none" and name not in ROBUST:
+            raise ValueError(f"FED.ROBUST_AGG {name!r}: one of {('none',) + ROBUST}")
+        trim_k = get("TRIM_K", 1)
+        if isinstance(trim_k, bool) or not isinstance(trim_k, int) or trim_k < 1:
+            raise ValueError(f"FED.TRIM_K {trim_k!r}: an integer >= 1")
+        if name == "none":
+            return None, trim_k
+        if name == "trimmed_mean" and 2 * trim_k >= self.num_clients:
+            raise ValueError(f"FED.TRIM_K {trim_k}: trimmed_mean drops 2 * TRIM_K of the FED.NUM_CLIENTS = "
+                             f"{self.num_clients} values and must leave one")
+        if self.num_clients > 64:
+            raise ValueError(f"FED.NUM_CLIENTS {self.num_clients}: FED.ROBUST_AGG sorts up to 64 clients per coordinate")
+        mode = get("AGGREGATION", "ordered")
+        if mode != "ordered":
+            raise ValueError(f'FED.AGGREGATION {mode!r}: FED.ROBUST_AGG needs "ordered" (a sum has lost the clients\' '
+                             "values)")
+        spec = get("CLIENT_WEIGHTS", "uniform")
+        if not (isinstance(spec, str) and spec.strip().lower() == "uniform"):
+            raise ValueError(f'FED.CLIENT_WEIGHTS {spec!r}: FED.ROBUST_AGG needs "uniform" (a weighted median is a '
+                             "different statistic)")
+        if self.rank == 0:
+            print("[INFO] Robust aggregation: coordinate-wise " +
+                  ("median" if name == "median" else f"trimmed mean, {trim_k} of {self.num_clients} cut at either end"))
+        return name, trim_k
+
     def build_model(self):
         """trainers/maple_fed.py:164-176, plus the options the reference lacks (all off by default):
-        FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.) and
-        FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.)."""
+        FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
+        FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
+        (coordinate-wise median / trimmed mean, Yin et al.)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
         if mu < 0.0 or mu != mu:
             raise ValueError(f"FED.PROX_MU {mu}: the FedProx coefficient is >= 0 (0 = off)")
         server_opt, server_hp = self._server_opt_cfg(get)
+        robust, trim_k = self._robust_cfg(get)
         spec = get("CLIENT_WEIGHTS", "uniform")
         self.client_weights = resolve_client_weights(spec, self._client_sample_counts(spec), self.num_clients)
         if self.client_weights is not None and self.rank == 0:
@@ -649,8 +682,8 @@ class MaPLeFederated(TrainerX):
             server_opt, c0.engine, lr=server_hp["FED.SERVER_LR"], beta1=server_hp["FED.SERVER_MOMENTUM"],
             beta2=server_hp["FED.SERVER_BETA2"], tau=server_hp["FED.SERVER_TAU"])
         self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id],
-                                 server=self.server) for c in self.clients]
-        self.exchange = FedAvgExchange(self.fed, mode=mode)
+                                 server=self.server, robust=robust, trim_k=trim_k) for c in self.clients]
+        self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k)
         if mu > 0.0:
             # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
             # pointers go in before a client captures its training step

@@ -330,6 +330,30 @@ int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* p32, int64_
 /* holds every client's packed bucket (an all-gather of mf_fedavg_pack outputs)                      */
 int mf_fedavg_reduce_ordered(const float* gathered, int nclients, int64_t stride, int64_t n, float* out,
                              void* stream);
+/* Robust aggregation: the coordinate-wise median and beta-trimmed mean of Yin, Chen, Ramchandran, Bartlett
+ * ("Byzantine-Robust Distributed Learning: Towards Optimal Statistical Rates", ICML 2018) over the image
+ * mf_fedavg_reduce_ordered sums (gathered[c * stride + i], c < nclients <= 64, i < n).  Per coordinate i, with the
+ * nclients fp32 values v_c:
+ *   - a NaN of any sign or payload marks client c absent; m = the number of present values (+-Inf are present);
+ *   - the present values are sorted ascending in the IEEE total order (-0 before +0): s_0 <= ... <= s_{m-1};
+ *   - k = min(trim_k, (m - 1) / 2) (integer division; k = 0 when m = 0): a trim that would leave nothing degrades to
+ *     the median, so a large trim_k is the median (for even m the fp32 mean of the two middle values);
+ *   - acc = s_k; acc += s_j for j = k + 1 .. m - 1 - k in ascending order, one IEEE fp32 add each (no fused
+ *     multiply-add; a lone -0 stays -0);
+ *   - out[i] = acc / float(m - 2k), correctly rounded; m = 0 gives +0;
+ *   - out[count_pos] = float(m) instead (count_pos < 0: no such element).
+ * A sum in sorted order depends on neither the client order nor on how the clients are laid out over the ranks.
+ * gathered and out must not overlap.  16-byte loads when stride % 4 == 0 and both pointers are 16-byte aligned
+ * (up to 16 clients), 4-byte loads otherwise and on the ragged tail; the same bits either way.
+ * Errors: nclients < 1 or > 64, trim_k < 0, n < 0 or stride < n, count_pos >= n.                               */
+int mf_fedavg_reduce_trimmed(const float* gathered, int nclients, int64_t stride, int64_t n, int trim_k,
+                             int64_t count_pos, float* out, void* stream);
+/* The bucket of the robust aggregation, n + 2 floats (n = n16 + n32): mf_fedavg_pack_weighted's layout at weight 1,
+ * [float(trainables) | 1 | 1], and an invalid client writes the quiet NaN 0x7fc00000 (absent) into all of them.
+ * Reduced by mf_fedavg_reduce_trimmed with count_pos at the last element it reads [statistic | 1 | m], which
+ * mf_fedavg_unpack_weighted and mf_fedopt_step / mf_fedopt_deliver (weighted = 1) consume as they are.          */
+int mf_fedavg_pack_robust(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
+                          float* bucket, void* stream);
 int mf_nonfinite_flag(const void* x, int64_t n, int is16, int* flag, void* stream);
 
 /* ---- image transforms (data step before the path) ---------------------
