@@ -226,6 +226,19 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # "median" (coordinate-wise) or "trimmed_mean" (coordinate-wise, the TRIM_K smallest and
                            # the TRIM_K largest of the clients' values dropped; 2 * TRIM_K < NUM_CLIENTS)
                            ROBUST_AGG="none", TRIM_K=1,
+                           # DP-FedAvg (McMahan, Ramage, Talwar, Zhang, ICLR 2018).  DP_CLIP: the L2 bound S every
+                           # client's update w_k - w_global is clipped to before it is packed; 0 = off.  On its own
+                           # it is norm bounding (Sun et al., 2019) and combines with every option above
+                           DP_CLIP=0.0,
+                           # the noise multiplier z: Gaussian noise of standard deviation z * DP_CLIP on every summed
+                           # coordinate, once per round; 0 = off.  Needs DP_CLIP > 0, CLIENT_WEIGHTS "uniform" and
+                           # ROBUST_AGG "none"
+                           DP_NOISE_MULTIPLIER=0.0,
+                           # the delta at which each round's log reports the cumulative epsilon; in (0, 1)
+                           DP_DELTA=1e-5,
+                           # seed of the noise stream; -1 = max(SEED, 0).  It comes from this file: a reproducible
+                           # simulation of the mechanism, not a hardened deployment
+                           DP_SEED=-1,
                            # size of each client's synthetic test split (no DATASET.ROOT); 0: one test batch
                            SYNTHETIC_TEST_IMAGES=0,
                            # > 0: the synthetic splits repeat that many generated images (bench timing runs)

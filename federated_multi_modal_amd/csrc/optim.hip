@@ -262,23 +262,37 @@ __global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f
 template <bool WEIGHTED>
 constexpr int TAIL = WEIGHTED ? 2 : 1;
 
-template <bool WEIGHTED, bool ABSENT = false>
+// CLIP (DP-FedAvg, McMahan et al., ICLR 2018): the client's update x - g is scaled by s = *scale (mf_dp_update_scale's
+// out[1], read on the device) before it is packed, and the bucket still holds weights: y = g + s * (x - g), three
+// separately rounded fp32 operations.  s >= 1 selects x itself, so a client inside the bound packs the bits the
+// other instantiations pack.  g16 / g32 / scale are read by CLIP only (null otherwise).
+template <bool WEIGHTED, bool ABSENT = false, bool CLIP = false>
 __global__ void pack_kernel(const f16* __restrict__ p16, int64_t n16, const float* __restrict__ p32, int64_t n32,
-                            const int* __restrict__ invalid, float* __restrict__ bucket, float w) {
+                            const int* __restrict__ invalid, float* __restrict__ bucket, float w,
+                            const f16* __restrict__ g16 = nullptr, const float* __restrict__ g32 = nullptr,
+                            const float* __restrict__ scale = nullptr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = n16 + n32;
   const bool bad = invalid && invalid[0] != 0;
   const float none = ABSENT ? __int_as_float(0x7fc00000) : 0.f;
-  const auto weigh = [&](float x) {
+  float s = 1.f;
+  if constexpr (CLIP) s = scale[0];
+  const auto weigh = [&](float x, float g) {
+    if constexpr (CLIP) {
+      const float d = x - g;
+      const float sd = s * d;
+      const float y = g + sd;
+      x = s >= 1.f ? x : y;
+    }
     if constexpr (WEIGHTED)
       return w * x;
     else
       return x;
   };
   if (i < n16)
-    bucket[i] = bad ? none : weigh((float)p16[i]);
+    bucket[i] = bad ? none : weigh((float)p16[i], CLIP ? (float)g16[i] : 0.f);
   else if (i < n)
-    bucket[i] = bad ? none : weigh(p32[i - n16]);
+    bucket[i] = bad ? none : weigh(p32[i - n16], CLIP ? g32[i - n16] : 0.f);
   else if (i == n)
     bucket[i] = bad ? none : (WEIGHTED ? w : 1.f);
   else if (WEIGHTED && i == n + 1)
@@ -880,6 +894,33 @@ extern "C" int mf_fedavg_pack_robust(const void* p16, int64_t n16, const float* 
   if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack_robust: negative size", -1);
   pack_kernel<true, true><<<nblk(n16 + n32 + TAIL<true>), 256, 0, (hipStream_t)stream>>>(
       (const f16*)p16, n16, p32, n32, invalid_flag, bucket, 1.f);
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+// DP-FedAvg's pack: the client's update clipped by *scale_ptr (mf_dp_update_scale's out + 1), in the bucket layout
+// `layout` (0 plain, 1 weighted, 2 robust); with *scale_ptr >= 1 the bits of the three entry points above
+extern "C" int mf_fedavg_pack_clipped(const void* p16, int64_t n16, const float* p32, int64_t n32, const void* g16,
+                                      const float* g32, const int* invalid_flag, const float* scale_ptr, float weight,
+                                      int layout, float* bucket, void* stream) {
+  if (n16 < 0 || n32 < 0) return mf_set_error("mf_fedavg_pack_clipped: negative size", -1);
+  if (layout < 0 || layout > 2) return mf_set_error("mf_fedavg_pack_clipped: layout is 0, 1 or 2", -1);
+  if (layout == 1 && (!(weight > 0.f) || __builtin_isinf(weight)))
+    return mf_set_error("mf_fedavg_pack_clipped: weight not in (0, inf)", -1);
+  if (!scale_ptr) return mf_set_error("mf_fedavg_pack_clipped: null scale pointer", -1);
+  if (!bucket || (n16 > 0 && (!p16 || !g16)) || (n32 > 0 && (!p32 || !g32)))
+    return mf_set_error("mf_fedavg_pack_clipped: null bucket, weights or global copy", -1);
+  hipStream_t st = (hipStream_t)stream;
+  const f16 *p = (const f16*)p16, *g = (const f16*)g16;
+  if (layout == 0)
+    pack_kernel<false, false, true><<<nblk(n16 + n32 + TAIL<false>), 256, 0, st>>>(p, n16, p32, n32, invalid_flag,
+                                                                                  bucket, 1.f, g, g32, scale_ptr);
+  else if (layout == 1)
+    pack_kernel<true, false, true><<<nblk(n16 + n32 + TAIL<true>), 256, 0, st>>>(p, n16, p32, n32, invalid_flag,
+                                                                                bucket, weight, g, g32, scale_ptr);
+  else
+    pack_kernel<true, true, true><<<nblk(n16 + n32 + TAIL<true>), 256, 0, st>>>(p, n16, p32, n32, invalid_flag, bucket,
+                                                                               1.f, g, g32, scale_ptr);
   MF_CHECK_LAUNCH();
   return 0;
 }

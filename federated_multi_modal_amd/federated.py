@@ -77,6 +77,26 @@ equals a single-process restatement bit for bit at any layout (tests/test_fedavg
 the same kernel over its buckets staged contiguously, also for a single client: it is what turns the absence marks
 into a zero vote.  Not combined with "allreduce" (a sum has lost the per-client values) or with client weights (a
 weighted median is another statistic).
+
+DP-FedAvg (FedAvgBucket dp_clip / FedAvgExchange dp_std; FED.DP_CLIP and FED.DP_NOISE_MULTIPLIER, off by default):
+user-level differential privacy as McMahan, Ramage, Talwar and Zhang define it (ICLR 2018; Geyer et al. 2017).  Each
+client's update Delta_k = w_k - g against the round's starting weights g (the bucket's global copy) is clipped to the L2
+bound S, Gaussian noise of standard deviation z * S is added to the sum, and dp_epsilon reports the (eps, delta) this
+buys.  The clipping half alone bounds a client that scales its update (Sun et al., 2019), which no per-coordinate
+statistic does, so dp_clip combines with client weights, the robust aggregation, the server optimizer and FedProx.
+pack() runs mf_dp_update_scale (norm = ||Delta_k||_2 in two launches, s_k = S / norm when norm > S, else exactly 1; it
+stays on the device) and then mf_fedavg_pack_clipped, which packs g + s_k * Delta_k in the bucket's layout: the bucket
+keeps holding weights, because the sum over the m valid clients is m * g + sum_k s_k Delta_k and every reduce, unpack
+and server step downstream consumes it unchanged -- no second layout, no extra traffic.  s_k >= 1 selects the weight
+itself, so a bound nobody reaches gives the bits of the plain exchange.  The noise is counter-based: its value at global
+coordinate i is a function of (seed, round, i) alone (Philox4x32-10 -> Box-Muller, mf_dp_add_noise), so in the sharded
+chain rank r noises its own shard [r * S, r * S + S) between the reduce and the all_gather, "allreduce" noises the
+whole sum on every rank after the all_reduce, one process after its local sum, and every layout ends with the same
+bits; only the n summed coordinates are noised, never the weight sum, the vote or the padding.  The exchange counts
+its rounds (finish() advances the counter once; a late-failure re-exchange reuses the round's value, and only that
+second sum is ever unpacked) and carries {round, seed} in its state_dict, so a resumed run never reuses a noise
+stream.  The noise needs the plain mean: with client weights the sensitivity would be w_k S / sum w, and an order
+statistic has another one.
 """
 from __future__ import annotations
 
@@ -91,6 +111,27 @@ from . import ops
 MODES = ("ordered", "allreduce")
 ROBUST = ("median", "trimmed_mean")
 MEDIAN_TRIM = ops.MEDIAN_TRIM  # a trim no client count reaches: the trimmed reduce degrades it to the median
+
+
+def dp_epsilon(z: float, rounds: int, delta: float) -> float:
+    """The epsilon of `rounds` Gaussian mechanisms of noise multiplier z (standard deviation z * S on a sum of L2
+    sensitivity S), every client taking part in every round, at `delta`, by Renyi-DP composition (Mironov, CSF 2017):
+    each round is (alpha, alpha / (2 z^2))-RDP, T rounds add up, and the conversion eps = T alpha / (2 z^2) +
+    ln(1 / delta) / (alpha - 1) is least at alpha = 1 + z sqrt(2 ln(1 / delta) / T), which gives the closed form
+    eps = T / (2 z^2) + sqrt(2 T ln(1 / delta)) / z.  z = 0 gives inf; no round gives 0."""
+    z, delta = float(z), float(delta)
+    if isinstance(rounds, bool) or int(rounds) != rounds or rounds < 0:
+        raise ValueError(f"dp_epsilon: rounds {rounds!r}: an integer >= 0")
+    if math.isnan(z) or z < 0.0:
+        raise ValueError(f"dp_epsilon: noise multiplier {z}: >= 0")
+    if not 0.0 < delta < 1.0:
+        raise ValueError(f"dp_epsilon: delta {delta}: in (0, 1)")
+    if rounds == 0:
+        return 0.0
+    if z == 0.0:
+        return math.inf
+    t = float(rounds)
+    return t / (2.0 * z * z) + math.sqrt(2.0 * t * math.log(1.0 / delta)) / z
 
 
 def robust_trim(robust: Optional[str], trim_k: int, mode: str = "ordered", weighted: bool = False) -> Optional[int]:
@@ -127,6 +168,10 @@ class _HipKernels:
     fedopt_deliver = staticmethod(ops.fedopt_deliver)
     fedavg_pack_robust = staticmethod(ops.fedavg_pack_robust)
     fedavg_reduce_trimmed = staticmethod(ops.fedavg_reduce_trimmed)
+    dp_update_ws_floats = staticmethod(ops.dp_update_ws_floats)
+    dp_update_scale = staticmethod(ops.dp_update_scale)
+    fedavg_pack_clipped = staticmethod(ops.fedavg_pack_clipped)
+    dp_add_noise = staticmethod(ops.dp_add_noise)
 
 
 SERVER_OPTS = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
@@ -250,6 +295,8 @@ class FedAvgBucket:
     restatements to exercise the collective protocol on CPU ranks (gloo).  `weight` (finite, > 0) selects the
     sample-weighted layout and kernels (module docstring); None is the reference's plain mean.  `robust`
     ("median" | "trimmed_mean", with `trim_k` values cut at either end) selects the robust aggregation instead.
+    `dp_clip` (finite, > 0) clips the client's update against the global copy to that L2 norm before it is packed, in
+    whichever layout the bucket has (module docstring, DP-FedAvg).
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
@@ -257,9 +304,15 @@ class FedAvgBucket:
 
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None, kernels=_HipKernels,
                  mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None,
-                 server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1):
+                 server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1,
+                 dp_clip: Optional[float] = None):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
+        if dp_clip is not None:
+            dp_clip = float(dp_clip)
+            if not math.isfinite(dp_clip) or dp_clip <= 0.0:
+                raise ValueError(f"FedAvg dp_clip {dp_clip}: finite and > 0 (None: no clipping)")
+        self.dp_clip = dp_clip
         self.trim = robust_trim(robust, trim_k, mode, weight is not None)
         self.robust, self.trim_k = robust, trim_k
         if weight is not None:
@@ -289,6 +342,13 @@ class FedAvgBucket:
         self.count = self.buf[n + tail - 1:]
         self.flag = torch.zeros(1, device=dev, dtype=torch.int32)
         self.failed = False
+        # DP-FedAvg: {norm, scale, clipped} of the client's update, written and read on the device, and the norm's
+        # per-chunk partial sums
+        self.clip_out = self.clip_ws = None
+        if dp_clip is not None:
+            self.clip_out = torch.tensor([0.0, 1.0, 0.0], device=dev, dtype=torch.float32)
+            self.clip_ws = torch.zeros(kernels.dp_update_ws_floats(engine.n16, engine.n32), device=dev,
+                                       dtype=torch.float32)
         # the last global weights (what broadcast_weights would load): restored when a round fails
         self.global16 = engine.flat16.detach().clone()
         self.global32 = engine.flat32.detach().clone()
@@ -310,7 +370,14 @@ class FedAvgBucket:
             self.flag.zero_()
             self.k.nonfinite_flag(e.flat16, self.flag)
             self.k.nonfinite_flag(e.flat32, self.flag)
-        if self.robust is not None:
+        if self.dp_clip is not None and not failed:
+            # the update against the weights the round started from, its clip scale left on the device for the pack
+            self.k.dp_update_scale(e.flat16, self.global16, e.flat32, self.global32, self.dp_clip, self.clip_ws,
+                                   self.clip_out)
+            layout = "robust" if self.robust is not None else ("plain" if self.weight is None else "weighted")
+            self.k.fedavg_pack_clipped(e.flat16, e.flat32, self.global16, self.global32, self.flag,
+                                       self.clip_out[1:2], self.weight, layout, self.buf)
+        elif self.robust is not None:
             self.k.fedavg_pack_robust(e.flat16, e.flat32, self.flag, self.buf)
         elif self.weight is None:
             self.k.fedavg_pack(e.flat16, e.flat32, self.flag, self.buf)
@@ -352,6 +419,14 @@ class FedAvgBucket:
         """Valid clients of the last round (host sync)."""
         return int(round(float(self.count.item())))
 
+    def clip_stats(self):
+        """(norm, scale) of the update the last pack() clipped (host sync; for logging).  (nan, 1.0) without dp_clip
+        or when that pack was of a failed client, whose update was not measured."""
+        if self.dp_clip is None or self.failed:
+            return float("nan"), 1.0
+        norm, scale = self.clip_out[:2].tolist()
+        return norm, scale
+
     # -- this bucket alone
     @property
     def exchange(self) -> "FedAvgExchange":
@@ -392,9 +467,15 @@ class FedAvgExchange:
     """The exchange of one rank's buckets (its C clients, in client order) with every other rank's."""
 
     def __init__(self, buckets: Sequence[FedAvgBucket], group: Optional[dist.ProcessGroup] = None,
-                 mode: str = "ordered", shard_single: bool = False, robust: Optional[str] = None, trim_k: int = 1):
+                 mode: str = "ordered", shard_single: bool = False, robust: Optional[str] = None, trim_k: int = 1,
+                 dp_std: float = 0.0, dp_seed: int = 0):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
+        dp_std = float(dp_std)
+        if not math.isfinite(dp_std) or dp_std < 0.0:
+            raise ValueError(f"FedAvg dp_std {dp_std}: finite and >= 0")
+        if isinstance(dp_seed, bool) or not isinstance(dp_seed, int) or not 0 <= dp_seed < 2 ** 64:
+            raise ValueError(f"FedAvg dp_seed {dp_seed!r}: an integer in [0, 2**64)")
         self.b = list(buckets)
         assert self.b and len({x.pbuf.numel() for x in self.b}) == 1
         # one layout per exchange: every bucket weighted (n + 2 floats) or none (n + 1)
@@ -402,6 +483,18 @@ class FedAvgExchange:
         self.trim = robust_trim(robust, trim_k, mode, self.b[0].weight is not None)
         assert all(x.trim == self.trim for x in self.b), "the buckets and their exchange differ in robust / trim_k"
         b0 = self.b[0]
+        if dp_std > 0.0:
+            if any(x.dp_clip is None for x in self.b):
+                raise ValueError("FedAvg dp_std > 0 needs dp_clip on every bucket: unclipped updates have no sensitivity")
+            if b0.weight is not None:
+                raise ValueError("FedAvg dp_std > 0 with a client weight: the sensitivity would be w_k S / sum w")
+            if self.trim is not None:
+                raise ValueError("FedAvg dp_std > 0 with robust aggregation: an order statistic has a different "
+                                 "sensitivity")
+        # DP-FedAvg noise: N(0, dp_std^2) on each of the n summed coordinates, a function of (seed, round, coordinate)
+        self.dp_std, self.dp_seed, self.round = dp_std, dp_seed, 0
+        self.n = b0.bucket.numel()
+        self._noise_due = False
         self.group, self.mode, self.k = group, mode, b0.k
         self.C = len(self.b)
         self.world = _world(group)
@@ -464,6 +557,7 @@ class FedAvgExchange:
         """Launch the exchange of the packed buckets (asynchronously where the backend allows)."""
         self.started = True
         self.work = None
+        self._noise_due = self.dp_std > 0.0 and not self.sharded  # the sharded chain noises its shard itself
         if not self.distributed:
             return  # one process: the sum is formed in finish()
         if not self.sharded:
@@ -499,6 +593,11 @@ class FedAvgExchange:
             pos = self.count_pos - dist.get_rank(self.group) * self.S
             self.k.fedavg_reduce_trimmed(self.recv, self.world * self.C, self.trim, pos if 0 <= pos < self.S else -1,
                                          self.shard)
+        if self.dp_std > 0.0:  # this rank's part of the summed coordinates [0, n): global offset rank * S
+            first = dist.get_rank(self.group) * self.S
+            n_noise = min(max(self.n - first, 0), self.S)
+            if n_noise > 0:
+                self.k.dp_add_noise(self.shard[:n_noise], first, self.dp_seed, self.round, self.dp_std)
         if hs:
             out = torch.empty(self.total.numel(), dtype=torch.float32)
             dist.all_gather_into_tensor(out, self.shard.cpu(), group=self.group)
@@ -515,6 +614,9 @@ class FedAvgExchange:
                 self._local_sum()
             else:
                 self._local_robust()
+        if self._noise_due:  # "allreduce" and one process: the whole sum, the same bits on every rank
+            self._noise_due = False
+            self.k.dp_add_noise(self.total[:self.n], 0, self.dp_seed, self.round, self.dp_std)
         if self.total is not self.b[0].pbuf:
             for x in self.b:
                 x.pbuf.copy_(self.total)
@@ -548,6 +650,19 @@ class FedAvgExchange:
             self.start()
         self._complete()
         self.started = False
+        self.round += 1  # once per finished round: the late-failure re-exchange above used the same value
+
+    def state_dict(self) -> dict:
+        """The noise stream's position: plain numbers (torch.load(..., weights_only=True) reads it)."""
+        return {"round": self.round, "seed": self.dp_seed}
+
+    def load_state_dict(self, sd: dict):
+        """Continue a saved run's noise stream: its seed, and its round counter, so no (seed, round) pair recurs."""
+        rnd, seed = sd.get("round"), sd.get("seed")
+        for label, v, top in (("round", rnd, 2 ** 32), ("seed", seed, 2 ** 64)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < top:
+                raise ValueError(f"FedAvgExchange state: {label} {v!r} is not an integer in [0, {top})")
+        self.round, self.dp_seed = rnd, seed
 
     def n_valid(self) -> int:
         return self.b[0].n_valid()

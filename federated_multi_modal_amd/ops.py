@@ -883,5 +883,86 @@ def fedavg_pack_robust(p16, p32, invalid_flag, bucket):
     call("mf_fedavg_pack_robust", _p(p16), p16.numel(), _p(p32), p32.numel(), _p(invalid_flag), _p(bucket), _s())
 
 
+def dp_update_ws_floats(n16: int, n32: int) -> int:
+    """Floats of workspace dp_update_scale needs for buffers of these sizes."""
+    return int(call("mf_dp_update_ws_floats", int(n16), int(n32)))
+
+
+def _check_dp_pairs(p16, g16, p32, g32):
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    _check_flat("g16", g16, torch.float16, p16.numel())
+    _check_flat("g32", g32, torch.float32, p32.numel())
+
+
+def dp_update_scale(p16, g16, p32, g32, clip, ws, out):
+    """out = {norm, scale, clipped} of the update [p16 | p32] - [g16 | g32]: norm = its L2 norm, scale = clip / norm
+    when norm > clip, else exactly 1 (mf_dp_update_scale; two launches, no host synchronisation).  ws: fp32 of at
+    least dp_update_ws_floats(n16, n32) elements; out: 3 floats; both buffers of their own."""
+    import math
+    clip = float(clip)
+    if math.isnan(clip) or clip <= 0.0:
+        raise ValueError(f"clip: > 0 required, got {clip}")
+    _check_dp_pairs(p16, g16, p32, g32)
+    need = dp_update_ws_floats(p16.numel(), p32.numel())
+    if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"ws: contiguous fp32 of at least {need} floats required, got {ws.dtype} {tuple(ws.shape)}")
+    _check_flat("out", out, torch.float32, 3)
+    for name, t in (("ws", ws), ("out", out)):
+        for oname, o in (("p16", p16), ("g16", g16), ("p32", p32), ("g32", g32)) + ((("out", out),) if t is ws else ()):
+            if _overlap(t, o):
+                raise ValueError(f"{name}: a buffer of its own required (it overlaps {oname})")
+    ev = _hbm("dp_update_scale", p16.numel() * 4.0 + p32.numel() * 8.0)  # the weights and the global copy read once
+    call("mf_dp_update_scale", _p(p16), _p(g16), p16.numel(), _p(p32), _p(g32), p32.numel(), clip, _p(ws), _p(out),
+         _s())
+    _rec(ev)
+
+
+DP_LAYOUTS = {"plain": 0, "weighted": 1, "robust": 2}
+
+
+def fedavg_pack_clipped(p16, p32, g16, g32, invalid_flag, scale, weight, layout, bucket):
+    """The bucket of layout "plain" ([y | 1]), "weighted" ([w * y | w | 1]) or "robust" ([y | 1 | 1], an invalid
+    client all quiet NaNs) with y = g + s * (float(p) - float(g)), s = scale[0] read on the device (dp_update_scale's
+    out[1:2]); s >= 1 packs float(p) itself (mf_fedavg_pack_clipped).  weight is read by "weighted" only."""
+    import math
+    if layout not in DP_LAYOUTS:
+        raise ValueError(f"layout: one of {tuple(DP_LAYOUTS)}, got {layout!r}")
+    weight = 1.0 if layout != "weighted" else float(weight)
+    if not math.isfinite(weight) or weight <= 0.0:
+        raise ValueError(f"weight: finite and > 0 required, got {weight}")
+    _check_dp_pairs(p16, g16, p32, g32)
+    tail = 1 if layout == "plain" else 2
+    _check_flat("bucket", bucket, torch.float32, p16.numel() + p32.numel() + tail)
+    if scale is None or scale.dtype != torch.float32 or scale.numel() < 1:
+        raise ValueError("scale: an fp32 tensor (dp_update_scale's out[1:2]) required")
+    for oname, o in (("p16", p16), ("g16", g16), ("p32", p32), ("g32", g32), ("scale", scale)):
+        if _overlap(bucket, o):
+            raise ValueError(f"bucket: a buffer of its own required (it overlaps {oname})")
+    call("mf_fedavg_pack_clipped", _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16), _p(g32), _p(invalid_flag),
+         _p(scale), weight, DP_LAYOUTS[layout], _p(bucket), _s())
+
+
+def dp_add_noise(buf, offset, seed, round_, std):
+    """buf[j] += std * z(offset + j): z(i) the standard normal of global coordinate i under (seed, round), a
+    counter-based stream (Philox4x32-10 + Box-Muller, include/mapfed.h), so any split of a range over calls gives the
+    same bits (mf_dp_add_noise).  std = 0 launches nothing."""
+    import math
+    offset, seed, round_, std = int(offset), int(seed), int(round_), float(std)
+    if buf.dtype != torch.float32 or not buf.is_contiguous():
+        raise ValueError(f"buf: contiguous fp32 required, got {buf.dtype} {tuple(buf.shape)}")
+    if not 0 <= offset <= 2 ** 63 - 1 - buf.numel():
+        raise ValueError(f"offset: 0 to 2**63 - 1 - n required, got {offset}")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed: 0 to 2**64 - 1 required, got {seed}")
+    if not 0 <= round_ < 2 ** 32:
+        raise ValueError(f"round: 0 to 2**32 - 1 required, got {round_}")
+    if not math.isfinite(std) or std < 0.0:
+        raise ValueError(f"std: finite and >= 0 required, got {std}")
+    ev = _hbm("dp_add_noise", buf.numel() * 8.0)  # read and written once
+    call("mf_dp_add_noise", _p(buf), buf.numel(), offset, seed, round_, std, _s())
+    _rec(ev)
+
+
 def nonfinite_flag(x, flag):
     call("mf_nonfinite_flag", _p(x), x.numel(), int(x.dtype == torch.float16), _p(flag), _s())

@@ -35,7 +35,7 @@ from . import ops
 from .data import DATASET_CLASSES, SyntheticClientDataManager, unified_classnames
 from .engine import EngineConfig, MapleEngine
 from .federated import (ROBUST, SERVER_OPTS, FedAvgBucket, FedAvgExchange, FederatedAbort, ServerOptimizer,
-                        resolve_client_weights)
+                        dp_epsilon, resolve_client_weights)
 from .captions import caption_tokens, draw_caption_weights, has_captions
 from .modules import CustomCLIP
 from .schedule import HostLR
@@ -651,11 +651,75 @@ class MaPLeFederated(TrainerX):
                   ("median" if name == "median" else f"trimmed mean, {trim_k} of {self.num_clients} cut at either end"))
         return name, trim_k
 
+    def _dp_cfg(self, get):
+        """FED.DP_CLIP, DP_NOISE_MULTIPLIER, DP_DELTA and DP_SEED, validated: {"clip": S or None, "z", "std": the
+        noise's standard deviation float32(z) * float32(S), "delta", "seed"}.  ValueError naming the key for a
+        negative or non-finite value, noise without a clip bound, with client weights or with FED.ROBUST_AGG, and a
+        DP_DELTA outside (0, 1)."""
+        vals = {}
+        for key, default in (("DP_CLIP", 0.0), ("DP_NOISE_MULTIPLIER", 0.0), ("DP_DELTA", 1e-5)):
+            v = get(key, default)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"FED.{key} {v!r}: a number")
+            vals[key] = float(v)
+            if not math.isfinite(vals[key]) or vals[key] < 0.0:
+                raise ValueError(f"FED.{key} {v!r}: finite and >= 0")
+        clip, z, delta = vals["DP_CLIP"], vals["DP_NOISE_MULTIPLIER"], vals["DP_DELTA"]
+        if not 0.0 < delta < 1.0:
+            raise ValueError(f"FED.DP_DELTA {delta!r}: in (0, 1)")
+        seed = get("DP_SEED", -1)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not -1 <= seed < 2 ** 64:
+            raise ValueError(f"FED.DP_SEED {seed!r}: an integer in [0, 2**64), or -1 for max(SEED, 0)")
+        if seed < 0:
+            seed = max(int(getattr(getattr(self, "cfg", None), "SEED", -1)), 0)
+        if z > 0.0:
+            if clip == 0.0:
+                raise ValueError(f"FED.DP_CLIP 0: FED.DP_NOISE_MULTIPLIER {z:g} needs a clip bound (the noise's "
+                                 "standard deviation is DP_NOISE_MULTIPLIER * DP_CLIP)")
+            spec = get("CLIENT_WEIGHTS", "uniform")
+            if not (isinstance(spec, str) and spec.strip().lower() == "uniform"):
+                raise ValueError(f'FED.CLIENT_WEIGHTS {spec!r}: FED.DP_NOISE_MULTIPLIER needs "uniform" (a weighted '
+                                 "client's sensitivity would be w_k S / sum w)")
+            name = get("ROBUST_AGG", "none")
+            if not (isinstance(name, str) and name.strip().lower() == "none"):
+                raise ValueError(f'FED.ROBUST_AGG {name!r}: FED.DP_NOISE_MULTIPLIER needs "none" (an order statistic '
+                                 "has a different sensitivity)")
+        std = float(torch.tensor(z, dtype=torch.float32) * torch.tensor(clip, dtype=torch.float32))
+        if not math.isfinite(std):
+            raise ValueError(f"FED.DP_NOISE_MULTIPLIER {z:g}: times FED.DP_CLIP {clip:g} is not finite in fp32")
+        if clip > 0.0 and self.rank == 0:
+            line = f"[INFO] DP-FedAvg: client updates clipped to L2 norm {clip:g}"
+            if z > 0.0:
+                line += (f", Gaussian noise z = {z:g} (std {std:g}) on the sum, seed {seed}; one round is "
+                         f"eps = {dp_epsilon(z, 1, delta):.4g} at delta = {delta:g}")
+            print(line)
+        return {"clip": clip if clip > 0.0 else None, "z": z, "std": std, "delta": delta, "seed": seed}
+
+    def _dp_report(self, round_no: int, n_valid: int):
+        """Rank 0's lines of a round under FED.DP_CLIP: its local clients' update norms and whether each was clipped,
+        and with noise the cumulative epsilon over the rounds that aggregated (host syncs: after the round's wait)."""
+        dp = getattr(self, "dp", None)
+        if dp is None or dp["clip"] is None:
+            return
+        self.dp_rounds = getattr(self, "dp_rounds", 0) + (1 if n_valid > 0 else 0)
+        if self.rank != 0:
+            return
+        parts = []
+        for c, fed in zip(self.clients, self.fed):
+            norm, scale = fed.clip_stats()
+            parts.append(f"client {c.client_id}: " + ("failed" if norm != norm else
+                                                      f"{norm:.6g} ({'clipped, scale %.6g' % scale if scale < 1.0 else 'kept'})"))
+        print(f"[Round {round_no}] DP update norms (bound {dp['clip']:g}): " + ", ".join(parts))
+        if dp["z"] > 0.0:
+            print(f"[Round {round_no}] DP epsilon = {dp_epsilon(dp['z'], self.dp_rounds, dp['delta']):.6g} at delta = "
+                  f"{dp['delta']:g} after {self.dp_rounds} aggregated round(s)")
+
     def build_model(self):
         """trainers/maple_fed.py:164-176, plus the options the reference lacks (all off by default):
         FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
         FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
-        (coordinate-wise median / trimmed mean, Yin et al.)."""
+        (coordinate-wise median / trimmed mean, Yin et al.), and FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
+        McMahan et al. 2018)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
@@ -663,6 +727,8 @@ class MaPLeFederated(TrainerX):
             raise ValueError(f"FED.PROX_MU {mu}: the FedProx coefficient is >= 0 (0 = off)")
         server_opt, server_hp = self._server_opt_cfg(get)
         robust, trim_k = self._robust_cfg(get)
+        self.dp = self._dp_cfg(get)
+        self.dp_rounds = 0  # rounds that aggregated (n_valid > 0): what the reported epsilon composes over
         spec = get("CLIENT_WEIGHTS", "uniform")
         self.client_weights = resolve_client_weights(spec, self._client_sample_counts(spec), self.num_clients)
         if self.client_weights is not None and self.rank == 0:
@@ -682,8 +748,10 @@ class MaPLeFederated(TrainerX):
             server_opt, c0.engine, lr=server_hp["FED.SERVER_LR"], beta1=server_hp["FED.SERVER_MOMENTUM"],
             beta2=server_hp["FED.SERVER_BETA2"], tau=server_hp["FED.SERVER_TAU"])
         self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id],
-                                 server=self.server, robust=robust, trim_k=trim_k) for c in self.clients]
-        self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k)
+                                 server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"])
+                    for c in self.clients]
+        self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k, dp_std=self.dp["std"],
+                                       dp_seed=self.dp["seed"])
         if mu > 0.0:
             # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
             # pointers go in before a client captures its training step
@@ -778,6 +846,7 @@ class MaPLeFederated(TrainerX):
             else:
                 print("All clients failed! Reverting to previous global model.")
                 self.nan_stats["skipped_rounds"] += 1
+            self._dp_report(round_idx + 1, n_valid)
             self.global_weights = self.clients[0].model.state_dict()
             t_gt = time.perf_counter()
             if self.rank == 0:
@@ -893,7 +962,10 @@ class MaPLeFederated(TrainerX):
         ckpt = {"epoch": self.cfg.OPTIM.MAX_EPOCH, "state_dict": sd, "optimizer": None, "scheduler": None,
                 "val_result": val_result, "cfg": self.cfg.dump(),
                 # the FedOpt server state (fp32 master copy and moments; CPU tensors and numbers); None when off
-                "server_optimizer": None if server is None else server.state_dict()}
+                "server_optimizer": None if server is None else server.state_dict(),
+                # the noise stream's position {round, seed} and the rounds the epsilon composes over, so that a resumed
+                # run never reuses a (seed, round) pair; None without an exchange that counts rounds
+                "dp": self._dp_state()}
         fpath = osp.join(target, f"model.pth.tar-{self.cfg.OPTIM.MAX_EPOCH}")
         torch.save(ckpt, fpath)
         with open(osp.join(target, "checkpoint"), "w") as f:
@@ -901,6 +973,12 @@ class MaPLeFederated(TrainerX):
         if self.cfg.VERBOSE:
             print(f"Model saved to {target}")
         return fpath
+
+    def _dp_state(self):
+        exchange = getattr(self, "exchange", None)
+        if not hasattr(exchange, "state_dict"):
+            return None
+        return dict(exchange.state_dict(), aggregated=int(getattr(self, "dp_rounds", 0)))
 
     def load_model(self, directory, epoch=None):
         """trainers/maple_fed.py:388-411."""
@@ -923,6 +1001,11 @@ class MaPLeFederated(TrainerX):
             if server is not None and ckpt.get("server_optimizer") is not None:
                 server.load_state_dict(ckpt["server_optimizer"])
                 print(f"Restored the {server.name} server optimizer state.")
+            exchange = getattr(self, "exchange", None)
+            if ckpt.get("dp") is not None and hasattr(exchange, "load_state_dict"):
+                exchange.load_state_dict(ckpt["dp"])
+                self.dp_rounds = int(ckpt["dp"].get("aggregated", 0))
+                print(f"Restored the DP noise stream at round {exchange.round}.")
             print("Broadcasted loaded global weights.")
         else:
             print("Warning: loaded global weights invalid! Skipping broadcast.")

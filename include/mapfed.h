@@ -354,6 +354,50 @@ int mf_fedavg_reduce_trimmed(const float* gathered, int nclients, int64_t stride
  * mf_fedavg_unpack_weighted and mf_fedopt_step / mf_fedopt_deliver (weighted = 1) consume as they are.          */
 int mf_fedavg_pack_robust(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
                           float* bucket, void* stream);
+/* ---- DP-FedAvg (McMahan, Ramage, Talwar, Zhang: "Learning Differentially Private Recurrent Language Models",
+ * ICLR 2018): per-client update clipping and Gaussian noise on the sum.  Every fp32 operation named below is one
+ * IEEE operation rounded on its own (no fused multiply-add), no float atomics, logf / sqrtf / sinf / cosf are the
+ * library functions, and every argument check returns before any launch.
+ *
+ * The update's L2 norm and the clip scale, two launches, no host synchronisation, bit-identical run to run:
+ *   d_i   = float(p_i) - float(g_i), one fp32 subtract, over [p16 | p32] against [g16 | g32];
+ *   norm  = sqrt(sum_i d_i * d_i): per chunk of 8192 elements of either buffer an fp32 partial sum (16-byte loads over
+ *           the middle that is 16-byte aligned in p and g alike, element loads for the ragged ends or throughout), then
+ *           one block adds the partial sums in chunk order in fp64 and rounds the square root to fp32;
+ *   out[0] = norm;  out[1] = scale = clip / norm (one fp32 divide) when norm > clip, else exactly 1.0f -- also for a
+ *           NaN norm, whose client the validity flag excludes;  out[2] = 1.0f when clipped, else 0.
+ * ws: mf_dp_update_ws_floats(n16, n32) floats (-1 for a negative size).  Errors: a negative size, clip not > 0, a
+ * null ws / out, a null buffer of a non-zero size.                                                               */
+int64_t mf_dp_update_ws_floats(int64_t n16, int64_t n32);
+int mf_dp_update_scale(const void* p16, const void* g16, int64_t n16, const float* p32, const float* g32, int64_t n32,
+                       float clip, float* ws, float* out, void* stream);
+/* The bucket of a clipped client.  layout 0: mf_fedavg_pack's [y | 1]; 1: mf_fedavg_pack_weighted's
+ * [w * y | w | 1]; 2: mf_fedavg_pack_robust's [y | 1 | 1] (weight unread).  An invalid client writes zeros in layouts
+ * 0 and 1 and the quiet NaN 0x7fc00000 in layout 2, everywhere.  With s = *scale_ptr read on the device
+ * (mf_dp_update_scale's out + 1), per element x = float(p), g = float(global copy):
+ *   s >= 1:  y = x (a select: the bits of the three entry points above);
+ *   else:    y = g + s * (x - g): d = x - g, sd = s * d, y = g + sd, three fp32 operations;
+ * then the layout's w * y.  The bucket keeps holding weights: the sum over m valid clients is m * g + sum s_k d_k, so
+ * every reduce, unpack and server step consumes it unchanged.  ||y - g||_2 <= clip up to the rounding of g + sd, about
+ * sqrt(n) * 2^-24 * max|y|.  Errors: a negative size, layout outside 0..2, layout 1 with a weight outside (0, inf), a
+ * null scale_ptr, bucket, or buffer of a non-zero size.                                                           */
+int mf_fedavg_pack_clipped(const void* p16, int64_t n16, const float* p32, int64_t n32, const void* g16,
+                           const float* g32, const int* invalid_flag, const float* scale_ptr, float weight, int layout,
+                           float* bucket, void* stream);
+/* buf[j] = buf[j] + std * z(offset + j) for j in [0, n): one fp32 multiply and one fp32 add.  z(i), the standard
+ * normal of global coordinate i, depends on (seed, round, i) alone:
+ *   q = i >> 2, lane = i & 3;
+ *   (x0, x1, x2, x3) = Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC 2011; multipliers 0xD2511F53, 0xCD9E8D57, key
+ *     increments 0x9E3779B9, 0xBB67AE85) of the counter (q_lo, q_hi, round, 0) under the key (seed_lo, seed_hi);
+ *   u(x) = float(((x >> 9) << 1) | 1) * 2^-24, an odd multiple of 2^-24 in (0, 1), exact in fp32;
+ *   lanes 0, 1 take (a, b) = (x0, x1), lanes 2, 3 (x2, x3);  r = sqrtf(-2 * logf(u(a))), theta = 6.2831855f * u(b);
+ *   an even lane gives r * cosf(theta), an odd one r * sinf(theta).
+ * So any split of a coordinate range over calls, ranks or shards gives the same bits.  One thread owns one counter;
+ * a counter wholly inside the call at a 16-byte aligned address takes one 16-byte load and store, any other element
+ * accesses, with the same arithmetic; nothing outside buf[0, n) is touched.  std = 0 (or n = 0) launches nothing, so
+ * the buffer keeps its bits.  Errors: n < 0, offset < 0, offset + n > INT64_MAX, std negative or not finite, a null
+ * or misaligned buf.                                                                                             */
+int mf_dp_add_noise(float* buf, int64_t n, int64_t offset, uint64_t seed, uint32_t round, float std, void* stream);
 int mf_nonfinite_flag(const void* x, int64_t n, int is16, int* flag, void* stream);
 
 /* ---- image transforms (data step before the path) ---------------------
