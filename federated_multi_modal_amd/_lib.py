@@ -73,6 +73,10 @@ SIGNATURES = {
     "mf_dp_update_scale": [P, P, L, P, P, L, F, P, P, P],
     "mf_fedavg_pack_clipped": [P, L, P, L, P, P, P, P, F, I, P, P],
     "mf_dp_add_noise": [P, L, L, ctypes.c_uint64, ctypes.c_uint32, F, P],
+    "mf_compress_chunk_bytes": [L],
+    "mf_compress_quantize": [P, P, L, P, P, L, P, P, P, F, I, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, P, L, L,
+                             I, P],
+    "mf_compress_decode": [P, L, I, L, L, L, P, L, P, L, I, P, L, P],
     "mf_seq_grow": [P, P, P, P, I, I, I, I, I, P],
     "mf_seq_grow_bwd": [P, P, I, I, I, I, I, P],
     "mf_seq_scatter": [P, L, P, L, I, I, I, I, P],
@@ -85,9 +89,11 @@ SIGNATURES = {
 # functions that return a value, not a status
 _VALUE_FUNCS = {"mf_abi_version", "mf_layernorm_bwd_blocks", "mf_colsum_blocks", "mf_optim_chunk_bytes",
                 "mf_optim_chunk_elems", "mf_col_reduce_desc_bytes", "mf_small_linear_desc_bytes",
-                "mf_gemm_splitk_ws_floats", "mf_augment_ws_bytes", "mf_qkv_attention_supported", "mf_dp_update_ws_floats"}
+                "mf_gemm_splitk_ws_floats", "mf_augment_ws_bytes", "mf_qkv_attention_supported", "mf_dp_update_ws_floats",
+                "mf_compress_chunk_bytes"}
 # value functions whose return type is not int
-_RESTYPES = {"mf_augment_ws_bytes": ctypes.c_int64, "mf_dp_update_ws_floats": ctypes.c_int64}
+_RESTYPES = {"mf_augment_ws_bytes": ctypes.c_int64, "mf_dp_update_ws_floats": ctypes.c_int64,
+             "mf_compress_chunk_bytes": ctypes.c_int64}
 
 _LIB = None
 

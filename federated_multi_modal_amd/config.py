@@ -239,6 +239,19 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # seed of the noise stream; -1 = max(SEED, 0).  It comes from this file: a reproducible
                            # simulation of the mechanism, not a hardened deployment
                            DP_SEED=-1,
+                           # int8 compression of the FedAvg uplink (QSGD, Alistarh et al., NeurIPS 2017): "none" or
+                           # "int8" -- each client's update w_k - w_global travels as 8-bit codes with one fp32 scale
+                           # per 256 coordinates, 1 + 1/64 bytes per coordinate instead of 4.  The sharded "ordered"
+                           # exchange over several ranks moves fewer bytes; "allreduce" and one process only simulate
+                           # the arithmetic.  Not with DP_CLIP
+                           COMPRESS="none",
+                           # "nearest", or "stochastic" (unbiased; its bits follow COMPRESS_SEED, the round and the client)
+                           COMPRESS_ROUNDING="nearest",
+                           # keep each client's rounding error and add it to its next update (Seide et al. 2014;
+                           # Karimireddy et al., ICML 2019).  The residuals restart at zero when a run is resumed
+                           COMPRESS_ERROR_FEEDBACK=True,
+                           # seed of the stochastic rounding; -1 = max(SEED, 0)
+                           COMPRESS_SEED=-1,
                            # size of each client's synthetic test split (no DATASET.ROOT); 0: one test batch
                            SYNTHETIC_TEST_IMAGES=0,
                            # > 0: the synthetic splits repeat that many generated images (bench timing runs)

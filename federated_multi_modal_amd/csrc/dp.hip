@@ -7,6 +7,7 @@
 // transcendental functions are the correctly-specified library ones (logf, sqrtf, sinf, cosf), not the hardware
 // approximations.
 #include "mf_common.h"
+#include "philox.h"
 
 #pragma clang fp contract(off)
 
@@ -86,26 +87,6 @@ __global__ __launch_bounds__(256) void dp_scale_kernel(const float* __restrict__
     out[1] = clipped ? clip / norm : 1.f;
     out[2] = clipped ? 1.f : 0.f;
   }
-}
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy as 1, 2, 3", SC 2011)
-MF_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                          uint32_t (&x)[4]) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += W0;
-    k1 += W1;
-  }
-  x[0] = c0;
-  x[1] = c1;
-  x[2] = c2;
-  x[3] = c3;
 }
 
 // 23 random bits to an odd multiple of 2^-24: exact in fp32, in (0, 1)

@@ -97,6 +97,25 @@ its rounds (finish() advances the counter once; a late-failure re-exchange reuse
 second sum is ever unpacked) and carries {round, seed} in its state_dict, so a resumed run never reuses a noise
 stream.  The noise needs the plain mean: with client weights the sensitivity would be w_k S / sum w, and an order
 statistic has another one.
+
+int8 compression of the uplink with error feedback (FedAvgBucket compress="int8"; FED.COMPRESS, off by default): the
+update u = (w_k - g) + e against the bucket's global copy is quantised to 8 bits per coordinate with one fp32 scale per
+block of 256 coordinates, rounded to nearest or stochastically (QSGD, Alistarh et al., NeurIPS 2017; the rounding bits
+are a function of (seed, round, client, coordinate) alone, Philox again), and the rounding error e' = u - scale * q
+stays with the client as next round's residual (Seide et al. 2014; Karimireddy et al., ICML 2019).  pack() runs
+mf_compress_quantize, which writes the codes, the scales and a {weight, vote} tail straight into the exchange's uint8
+send image [destination rank][client][chunk], chunk = S + S / 64 + 8 bytes for a shard of S coordinates (S is then a
+multiple of 256): 1 + 1/64 bytes per coordinate where the fp32 bucket moves 4.  In the sharded "ordered" chain the
+all_to_all moves that image and the receiver rebuilds, with mf_compress_decode and the global copy every rank holds, the
+fp32 image g + scale * q of its shard of every client -- exactly what the pack kernels would have sent for those weights
+-- so the ordered or trimmed reduce, the all_gather (the downlink stays fp32), the unpack and the server step run
+unchanged, and client weights, the robust aggregation, the server optimizers and FedProx combine with it as they are.
+One process and "allreduce" decode each bucket locally right away and then run as before: the arithmetic of
+compression, none of its savings.  pack() reads e and writes e' to a second buffer; unpack() swaps the two, once per
+round and only for a client that did not fail, so a late-failure re-pack reads the same e, weights, global copy and
+round, reproduces the same codes, and the residual is applied once; an invalid or failed client sends nothing (codes,
+scales and vote 0) and keeps its residual.  Not combined with dp_clip / dp_std: a quantised, fed-back update no longer
+has an L2 norm within the bound.
 """
 from __future__ import annotations
 
@@ -111,6 +130,9 @@ from . import ops
 MODES = ("ordered", "allreduce")
 ROBUST = ("median", "trimmed_mean")
 MEDIAN_TRIM = ops.MEDIAN_TRIM  # a trim no client count reaches: the trimmed reduce degrades it to the median
+COMPRESS = ("int8",)
+COMPRESS_ROUNDINGS = tuple(ops.COMPRESS_ROUNDINGS)
+COMPRESS_BLOCK = ops.COMPRESS_BLOCK  # coordinates per quantisation block; a compressed shard is a multiple of it
 
 
 def dp_epsilon(z: float, rounds: int, delta: float) -> float:
@@ -172,6 +194,9 @@ class _HipKernels:
     dp_update_scale = staticmethod(ops.dp_update_scale)
     fedavg_pack_clipped = staticmethod(ops.fedavg_pack_clipped)
     dp_add_noise = staticmethod(ops.dp_add_noise)
+    compress_chunk_bytes = staticmethod(ops.compress_chunk_bytes)
+    compress_quantize = staticmethod(ops.compress_quantize)
+    compress_decode = staticmethod(ops.compress_decode)
 
 
 SERVER_OPTS = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
@@ -296,7 +321,10 @@ class FedAvgBucket:
     sample-weighted layout and kernels (module docstring); None is the reference's plain mean.  `robust`
     ("median" | "trimmed_mean", with `trim_k` values cut at either end) selects the robust aggregation instead.
     `dp_clip` (finite, > 0) clips the client's update against the global copy to that L2 norm before it is packed, in
-    whichever layout the bucket has (module docstring, DP-FedAvg).
+    whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8") sends the update as int8 codes
+    with block scales instead (module docstring): `compress_rounding` "nearest" | "stochastic", `error_feedback` keeps
+    the rounding error as a per-client residual (state_dict() / load_state_dict() carry it), `compress_seed` and
+    `client`, the global client index, select the stochastic rounding's bits.
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
@@ -305,9 +333,23 @@ class FedAvgBucket:
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None, kernels=_HipKernels,
                  mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None,
                  server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1,
-                 dp_clip: Optional[float] = None):
+                 dp_clip: Optional[float] = None, compress: Optional[str] = None, compress_rounding: str = "nearest",
+                 error_feedback: bool = True, compress_seed: int = 0, client: int = 0):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
+        if compress is not None and compress not in COMPRESS:
+            raise ValueError(f"FedAvg compress {compress!r}: None or one of {COMPRESS}")
+        if compress_rounding not in COMPRESS_ROUNDINGS:
+            raise ValueError(f"FedAvg compress_rounding {compress_rounding!r}: one of {COMPRESS_ROUNDINGS}")
+        if isinstance(compress_seed, bool) or not isinstance(compress_seed, int) or not 0 <= compress_seed < 2 ** 64:
+            raise ValueError(f"FedAvg compress_seed {compress_seed!r}: an integer in [0, 2**64)")
+        if isinstance(client, bool) or not isinstance(client, int) or not 0 <= client < 2 ** 31:
+            raise ValueError(f"FedAvg client {client!r}: the global client index, an integer in [0, 2**31)")
+        if compress is not None and dp_clip is not None:
+            raise ValueError("FedAvg compress with dp_clip: a quantised, fed-back update no longer has an L2 norm "
+                             "within the bound")
+        self.compress, self.compress_rounding, self.error_feedback = compress, compress_rounding, bool(error_feedback)
+        self.compress_seed, self.client = compress_seed, client
         if dp_clip is not None:
             dp_clip = float(dp_clip)
             if not math.isfinite(dp_clip) or dp_clip <= 0.0:
@@ -335,7 +377,9 @@ class FedAvgBucket:
         # aggregation uses that layout at weight 1 ([bucket | 1 | count | padding])
         self.weighted = weight is not None or robust is not None
         tail = 2 if self.weighted else 1
-        padded = -(-(n + tail) // self.world) * self.world
+        # compressed: a shard is a whole number of quantisation blocks
+        quantum = self.world * (COMPRESS_BLOCK if compress is not None else 1)
+        padded = -(-(n + tail) // quantum) * quantum
         self.pbuf = torch.zeros(padded, device=dev, dtype=torch.float32)
         self.buf = self.pbuf[:n + tail]
         self.bucket = self.buf[:n]
@@ -353,6 +397,15 @@ class FedAvgBucket:
         self.global16 = engine.flat16.detach().clone()
         self.global32 = engine.flat32.detach().clone()
         self._x: Optional[FedAvgExchange] = None
+        # int8 compression of the uplink: the error-feedback residual e and the buffer the quantiser writes e' to
+        # (unpack() swaps them once per round), and the exchange whose send image this bucket's pack() writes, with
+        # the bucket's place in it
+        self.resid = self.resid_next = None
+        if compress is not None and self.error_feedback:
+            self.resid = torch.zeros(n, device=dev, dtype=torch.float32)
+            self.resid_next = torch.zeros(n, device=dev, dtype=torch.float32)
+        self._resid_due = False
+        self._wire: Optional[tuple] = None
         if server is not None and (server.n16, server.n32) != (engine.n16, engine.n32):
             raise ValueError("FedAvgBucket: the server optimizer was built for other sizes")
         self.server = server
@@ -361,7 +414,8 @@ class FedAvgBucket:
     def pack(self, failed: bool = False):
         """Validity scan + pack.  failed=True: the client's local training raised (its weights are
         excluded, trainers/maple_fed.py:262-265); an invalid client contributes zeros and no vote
-        (:272-277)."""
+        (:272-277).  With compress the pack is the quantiser: it writes this client's chunks of the exchange's send
+        image and the next residual, and the fp32 bucket is filled by the decode."""
         e = self.e
         self.failed = failed
         if failed:
@@ -370,7 +424,18 @@ class FedAvgBucket:
             self.flag.zero_()
             self.k.nonfinite_flag(e.flat16, self.flag)
             self.k.nonfinite_flag(e.flat32, self.flag)
-        if self.dp_clip is not None and not failed:
+        if self.compress is not None:
+            # the update against the weights the round started from, as int8 codes and block scales straight into
+            # the exchange's send image; e is read, e' written: a late-failure re-pack reads the same e, weights,
+            # global copy and round and reproduces the codes, and unpack() commits e' once
+            if self._wire is None:
+                self.exchange  # this bucket alone: its exchange owns the image
+            x, slot = self._wire
+            self.k.compress_quantize(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
+                                     self.flag, self.weight, self.compress_rounding, self.compress_seed, x.round,
+                                     self.client, x.image, slot, x.S)
+            self._resid_due = self.resid is not None and not failed
+        elif self.dp_clip is not None and not failed:
             # the update against the weights the round started from, its clip scale left on the device for the pack
             self.k.dp_update_scale(e.flat16, self.global16, e.flat32, self.global32, self.dp_clip, self.clip_ws,
                                    self.clip_out)
@@ -405,6 +470,9 @@ class FedAvgBucket:
             self.k.fedavg_unpack(self.buf, e.flat16, e.flat32, self.global16, self.global32)
         else:
             self.k.fedavg_unpack_weighted(self.buf, e.flat16, e.flat32, self.global16, self.global32)
+        if self._resid_due:  # the residual of the codes that were exchanged, once per round; a failed client keeps its own
+            self.resid, self.resid_next = self.resid_next, self.resid
+            self._resid_due = False
         e.after_weights_loaded()
 
     def snapshot(self):
@@ -426,6 +494,25 @@ class FedAvgBucket:
             return float("nan"), 1.0
         norm, scale = self.clip_out[:2].tolist()
         return norm, scale
+
+    def state_dict(self) -> dict:
+        """The error-feedback residual as a CPU fp32 tensor (None without one); torch.load(..., weights_only=True)
+        reads it."""
+        return {"residual": None if self.resid is None else self.resid.detach().cpu().clone()}
+
+    def load_state_dict(self, sd: dict):
+        """A saved residual.  ValueError when this bucket keeps none, or for another size or dtype."""
+        t = sd.get("residual")
+        if t is None:
+            if self.resid is not None:
+                self.resid.zero_()
+            return
+        if self.resid is None:
+            raise ValueError("FedAvgBucket state: a residual for a bucket without error feedback")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != self.resid.numel():
+            raise ValueError(f"FedAvgBucket state: the residual is not fp32 of {self.resid.numel()} elements")
+        self.resid.copy_(t.reshape(-1))
+        self._resid_due = False
 
     # -- this bucket alone
     @property
@@ -449,6 +536,8 @@ class FedAvgBucket:
         self.pack(failed)
         if collective:
             self.exchange.start()
+        elif self.compress is not None:  # packed only: the bucket still has to hold the fp32 image of its codes
+            self._wire[0].decode_local()
 
     def finish(self, late_failed: Optional[bool] = None):
         """Wait for the exchange, then unpack.  late_failed: whether the client failed after start()
@@ -477,6 +566,9 @@ class FedAvgExchange:
         if isinstance(dp_seed, bool) or not isinstance(dp_seed, int) or not 0 <= dp_seed < 2 ** 64:
             raise ValueError(f"FedAvg dp_seed {dp_seed!r}: an integer in [0, 2**64)")
         self.b = list(buckets)
+        if len({None if x.compress is None else (x.compress, x.compress_rounding, x.error_feedback, x.compress_seed)
+                for x in self.b}) > 1:
+            raise ValueError("FedAvg compress: the buckets of one exchange differ in their compression settings")
         assert self.b and len({x.pbuf.numel() for x in self.b}) == 1
         # one layout per exchange: every bucket weighted (n + 2 floats) or none (n + 1)
         assert len({x.weight is None for x in self.b}) == 1, "weighted and unweighted buckets in one exchange"
@@ -507,8 +599,24 @@ class FedAvgExchange:
         self.sharded = self.distributed and mode == "ordered"
         self.side = None
         self.host_stage = False
+        # int8 compression of the uplink: one setting per exchange; the uint8 send image [dest rank][client][chunk] the
+        # buckets' packs write into, and under the sharded chain the image the all_to_all fills
+        self.compress = b0.compress
+        self.image = self.recv_image = None
+        if self.compress is not None:
+            if b0.compress_rounding == "stochastic" and len({x.client for x in self.b}) != self.C:
+                raise ValueError("FedAvg compress: two buckets of one exchange carry the same client index (their "
+                                 "rounding bits would coincide)")
+            self.layout = "robust" if b0.robust is not None else ("plain" if b0.weight is None else "weighted")
+            self.chunk = self.k.compress_chunk_bytes(self.S)
+            self.image = torch.zeros(self.world, self.C, self.chunk, device=dev, dtype=torch.uint8)
+            if self.sharded:
+                self.recv_image = torch.empty(self.world * self.C * self.chunk, device=dev, dtype=torch.uint8)
+            for j, x in enumerate(self.b):
+                x._wire = (self, j)
         # the exchange's send image: C == 1 sends the bucket itself; C > 1 stages [dest rank][client][shard]
-        self.stage = None if self.C == 1 else torch.empty(self.world, self.C, self.S, device=dev, dtype=torch.float32)
+        self.stage = None if self.C == 1 or self.compress is not None else torch.empty(
+            self.world, self.C, self.S, device=dev, dtype=torch.float32)
         # where the exchanged sum lands (C == 1: back into the bucket; C > 1: a total copied into every bucket)
         self.total = b0.pbuf if self.C == 1 else torch.empty(padded, device=dev, dtype=torch.float32)
         self.recv = self.shard = None
@@ -536,6 +644,15 @@ class FedAvgExchange:
             self.stage[:, j, :].copy_(x.pbuf.view(self.world, self.S))
         return self.stage.view(-1)
 
+    def decode_local(self):
+        """Compressed, without the sharded chain (one process, "allreduce"): every local bucket's chunks decoded into
+        its own fp32 bucket, g + scale * q in the bucket's layout, which the existing paths then consume.  No traffic
+        is saved here: the compression is simulated."""
+        img = self.image.view(-1)
+        for j, x in enumerate(self.b):
+            self.k.compress_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
+                                   x.global16, x.global32, self.layout, x.pbuf, self.S)
+
     def _local_sum(self) -> torch.Tensor:
         """The rank's buckets summed in client order (== torch.stack(...) order over these clients)."""
         if self.C == 1:
@@ -561,12 +678,14 @@ class FedAvgExchange:
         if not self.distributed:
             return  # one process: the sum is formed in finish()
         if not self.sharded:
+            if self.compress is not None:
+                self.decode_local()
             src = self._local_sum()
             if src is not self.total:
                 self.total.copy_(src)
             self.work = dist.all_reduce(self.total, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
             return
-        send = self._send_image()
+        send = self._send_image() if self.compress is None else self.image.view(-1)  # the packs wrote it in place
         if self.side is not None:
             # the whole chain on the side stream: the current stream only waits for it in finish()
             self.side.wait_stream(torch.cuda.current_stream(send.device))
@@ -582,11 +701,24 @@ class FedAvgExchange:
         under gloo it is a host wait, and with device buckets (host_stage) the collectives move host copies.
         Returns the all_gather's work handle (None when it completed here)."""
         hs = self.host_stage
-        recv = torch.empty(self.recv.numel(), dtype=torch.float32) if hs else self.recv
-        a2a = dist.all_to_all_single(recv, send.cpu() if hs else send, group=self.group, async_op=True)
-        a2a.wait()
-        if hs:
-            self.recv.copy_(recv)
+        if self.compress is None:
+            recv = torch.empty(self.recv.numel(), dtype=torch.float32) if hs else self.recv
+            a2a = dist.all_to_all_single(recv, send.cpu() if hs else send, group=self.group, async_op=True)
+            a2a.wait()
+            if hs:
+                self.recv.copy_(recv)
+        else:
+            # the uint8 image moves; the receiver rebuilds the fp32 image g + scale * q of its shard of every client
+            # from the global copy every rank holds, and the rest of the chain reads it as it reads a received one
+            rimg = torch.empty(self.recv_image.numel(), dtype=torch.uint8) if hs else self.recv_image
+            a2a = dist.all_to_all_single(rimg, send.cpu() if hs else send, group=self.group, async_op=True)
+            a2a.wait()
+            if hs:
+                self.recv_image.copy_(rimg)
+            b0 = self.b[0]
+            self.k.compress_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
+                                   dist.get_rank(self.group) * self.S, 0, b0.global16, b0.global32, self.layout,
+                                   self.recv, self.S)
         if self.trim is None:
             self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
         else:  # the robust statistic of this rank's shard; the vote element, if it lies in this shard, counts
@@ -610,6 +742,8 @@ class FedAvgExchange:
             self.work.wait()
             self.work = None
         if not self.distributed:
+            if self.compress is not None:
+                self.decode_local()
             if self.trim is None:
                 self._local_sum()
             else:

@@ -695,6 +695,51 @@ class MaPLeFederated(TrainerX):
             print(line)
         return {"clip": clip if clip > 0.0 else None, "z": z, "std": std, "delta": delta, "seed": seed}
 
+    def _compress_cfg(self, get):
+        """FED.COMPRESS, COMPRESS_ROUNDING, COMPRESS_ERROR_FEEDBACK and COMPRESS_SEED, validated: {"compress": "int8" or
+        None, "rounding", "error_feedback", "seed"}.  ValueError naming the key for an unknown name, a flag that is no
+        bool, a seed outside [0, 2**64) other than -1, and FED.COMPRESS together with FED.DP_CLIP."""
+        from .federated import COMPRESS, COMPRESS_ROUNDINGS
+        name = get("COMPRESS", "none")
+        if not isinstance(name, str) or name.strip().lower() not in ("none",) + COMPRESS:
+            raise ValueError(f'FED.COMPRESS {name!r}: "none" or one of {COMPRESS}')
+        name = name.strip().lower()
+        rounding = get("COMPRESS_ROUNDING", "nearest")
+        if not isinstance(rounding, str) or rounding.strip().lower() not in COMPRESS_ROUNDINGS:
+            raise ValueError(f"FED.COMPRESS_ROUNDING {rounding!r}: one of {COMPRESS_ROUNDINGS}")
+        rounding = rounding.strip().lower()
+        ef = get("COMPRESS_ERROR_FEEDBACK", True)
+        if not isinstance(ef, bool):
+            raise ValueError(f"FED.COMPRESS_ERROR_FEEDBACK {ef!r}: True or False")
+        seed = get("COMPRESS_SEED", -1)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not -1 <= seed < 2 ** 64:
+            raise ValueError(f"FED.COMPRESS_SEED {seed!r}: an integer in [0, 2**64), or -1 for max(SEED, 0)")
+        if seed < 0:
+            seed = max(int(getattr(getattr(self, "cfg", None), "SEED", -1)), 0)
+        if name != "none":
+            clip = get("DP_CLIP", 0.0)
+            if isinstance(clip, (int, float)) and not isinstance(clip, bool) and clip > 0.0:
+                raise ValueError(f"FED.COMPRESS {name!r}: not with FED.DP_CLIP {clip:g} (a quantised, fed-back update no "
+                                 "longer has an L2 norm within the bound)")
+        return {"compress": None if name == "none" else name, "rounding": rounding, "error_feedback": ef, "seed": seed}
+
+    def _compress_report(self):
+        """Rank 0's line under FED.COMPRESS, once: the uplink bytes per client and round with and without compression."""
+        cp = getattr(self, "compress", None)
+        if cp is None or cp["compress"] is None or self.rank != 0:
+            return
+        x, fed = self.exchange, self.fed[0]
+        plain, wire = 4 * fed.buf.numel(), x.world * x.chunk
+        how = cp["rounding"] + (", error feedback" if cp["error_feedback"] else ", no error feedback")
+        line = (f"[INFO] FedAvg uplink compression int8 ({how}): {wire} bytes per client and round instead of {plain} "
+                f"({plain / wire:.2f}x), the downlink stays fp32")
+        if not x.sharded:
+            line += "; this exchange decodes locally (one process or \"allreduce\"): simulated, no traffic is saved"
+        print(line)
+        if cp["error_feedback"]:
+            print("[INFO] FedAvg uplink compression: the error-feedback residuals are not checkpointed; a resumed run "
+                  "restarts them at zero")
+
     def _dp_report(self, round_no: int, n_valid: int):
         """Rank 0's lines of a round under FED.DP_CLIP: its local clients' update norms and whether each was clipped,
         and with noise the cumulative epsilon over the rounds that aggregated (host syncs: after the round's wait)."""
@@ -718,8 +763,8 @@ class MaPLeFederated(TrainerX):
         """trainers/maple_fed.py:164-176, plus the options the reference lacks (all off by default):
         FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
         FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
-        (coordinate-wise median / trimmed mean, Yin et al.), and FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
-        McMahan et al. 2018)."""
+        (coordinate-wise median / trimmed mean, Yin et al.), FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
+        McMahan et al. 2018) and FED.COMPRESS (int8 uplink compression with error feedback, Alistarh et al.)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
@@ -729,6 +774,7 @@ class MaPLeFederated(TrainerX):
         robust, trim_k = self._robust_cfg(get)
         self.dp = self._dp_cfg(get)
         self.dp_rounds = 0  # rounds that aggregated (n_valid > 0): what the reported epsilon composes over
+        self.compress = cp = self._compress_cfg(get)
         spec = get("CLIENT_WEIGHTS", "uniform")
         self.client_weights = resolve_client_weights(spec, self._client_sample_counts(spec), self.num_clients)
         if self.client_weights is not None and self.rank == 0:
@@ -748,10 +794,13 @@ class MaPLeFederated(TrainerX):
             server_opt, c0.engine, lr=server_hp["FED.SERVER_LR"], beta1=server_hp["FED.SERVER_MOMENTUM"],
             beta2=server_hp["FED.SERVER_BETA2"], tau=server_hp["FED.SERVER_TAU"])
         self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id],
-                                 server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"])
+                                 server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"],
+                                 compress=cp["compress"], compress_rounding=cp["rounding"],
+                                 error_feedback=cp["error_feedback"], compress_seed=cp["seed"], client=c.client_id)
                     for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k, dp_std=self.dp["std"],
                                        dp_seed=self.dp["seed"])
+        self._compress_report()
         if mu > 0.0:
             # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
             # pointers go in before a client captures its training step
@@ -996,6 +1045,11 @@ class MaPLeFederated(TrainerX):
             self.broadcast_weights(self.global_weights)
             for fed in getattr(self, "fed", []):
                 fed.snapshot()  # an all-failed round now reverts to the loaded weights
+            # the compression residuals are not in the checkpoint (one fp32 bucket per client, on every rank)
+            if any(getattr(fed, "resid", None) is not None for fed in getattr(self, "fed", [])):
+                for fed in self.fed:
+                    fed.load_state_dict({"residual": None})
+                print("The uplink compression's error-feedback residuals restart at zero.")
             # ... and the server optimizer starts from them, unless the checkpoint carries its state
             server = getattr(self, "server", None)
             if server is not None and ckpt.get("server_optimizer") is not None:

@@ -398,6 +398,65 @@ int mf_fedavg_pack_clipped(const void* p16, int64_t n16, const float* p32, int64
  * the buffer keeps its bits.  Errors: n < 0, offset < 0, offset + n > INT64_MAX, std negative or not finite, a null
  * or misaligned buf.                                                                                             */
 int mf_dp_add_noise(float* buf, int64_t n, int64_t offset, uint64_t seed, uint32_t round, float std, void* stream);
+/* ---- int8 compression of the FedAvg uplink with error feedback (QSGD: Alistarh, Grubic, Li, Tomioka, Vojnovic, NeurIPS
+ * 2017; error feedback: Seide et al. 2014, Karimireddy, Rebjock, Stich, Jaggi, ICML 2019).  Every fp32 operation named
+ * below is one IEEE operation rounded on its own (no fused multiply-add), no float atomics, plain vector stores only, and
+ * every argument check returns before any launch.
+ *
+ * Coordinates i in [0, n), n = n16 + n32, run over [fp16 trainables | fp32 trainables], the bucket's order.  The
+ * quantisation block is B = 256 consecutive coordinates; a block may straddle the fp16 / fp32 boundary, and coordinates
+ * >= n of the padded bucket [0, world * S) count as u = 0.  S, the shard length, is a multiple of 256.
+ *
+ * Quantise (x the client's weights, g the global copy, e its fp32 residual):
+ *   d_i = float(x_i) - float(g_i);  u_i = d_i + e_i (two fp32 operations; e_in == e_out == null: error feedback off,
+ *         e is neither read nor written and u_i = d_i);
+ *   per block: amax = max |u_i| (order-independent, exact), scale = amax / 127.0f (one divide); amax == 0 gives scale 0,
+ *         all codes 0 and e'_i = u_i;
+ *   t = u_i / scale (one divide), f = floorf(t);
+ *   rounding 0 (nearest):    q = rintf(t);
+ *   rounding 1 (stochastic): p = t - f (exact), q = f + (r_i < p ? 1 : 0), r_i = float(w >> 8) * 2^-24 in [0, 1), w the
+ *         word i & 3 of Philox4x32-10 (mf_dp_add_noise's generator) on the counter (c_lo, c_hi, round,
+ *         0x80000000 | client), c = i >> 2, under the key (seed_lo, seed_hi): the counter's last word keeps these streams
+ *         apart from the noise streams, client is the global client index, and the bits depend on (seed, round, client, i)
+ *         alone;
+ *   q = fminf(fmaxf(q, -127), 127) (amax / (amax / 127) can round above 127; a NaN becomes -127, so only finite values
+ *         are converted), stored as int8;
+ *   e'_i = u_i - scale * q (one multiply, one subtract), written to e_out, a second buffer (e_in is only read, so a
+ *         repeated call gives the same codes).
+ * A client whose *invalid_flag is set (read on the device) writes codes 0, scales 0, weight 0 and vote 0 and copies e to
+ * e' unchanged; no weight of it is read.
+ *
+ * Wire chunk per (destination rank r, client), mf_compress_chunk_bytes(S) = S + S / 64 + 8 bytes (-1 unless S is a
+ * positive multiple of 256): [S int8 codes | S / 256 fp32 scales | fp32 weight | fp32 vote], the codes and scales of the
+ * coordinates [r * S, r * S + S); weight = `weight` (1 for the plain and the robust layout), 0 if invalid; vote = 1, 0 if
+ * invalid; the two are replicated into every chunk.  mf_compress_quantize writes the `world` chunks of one client
+ * at image + r * rank_stride (bytes; image 4-byte aligned, rank_stride a multiple of 4): the exchange's send image
+ * [destination rank][local client][chunk] is written in place.  One wave64 per block, four coordinates per lane (one
+ * Philox counter), the max a wave reduction, the four codes one 32-bit store; 8- or 16-byte loads and stores wherever
+ * an address allows, element accesses otherwise, the same bits either way.  Errors: negative sizes, S not a positive
+ * multiple of 256, world < 1, world * S < n, an unknown rounding, a weight outside (0, inf), client >= 2^31, a null or
+ * misaligned image, a null flag, a null buffer of a non-zero size, one residual pointer without the other or both the
+ * same.
+ *
+ * Decode: nclients chunks at image + c * chunk_stride (bytes) into out + c * out_stride (floats), S floats each: chunk
+ * c holds the coordinates i = first + c * first_step + j, j < S (first_step 0: every client's shard `first` of a
+ * received image; first_step S with chunk_stride the rank stride: one client's whole bucket).  It writes the fp32 image
+ * mf_fedavg_reduce_ordered / _trimmed read, in layout 0 (mf_fedavg_pack), 1 (mf_fedavg_pack_weighted) or 2
+ * (mf_fedavg_pack_robust):
+ *   i < n:       y = float(g_i) + scale * q (one multiply, one add), then w * y (layout 1) or y (0, 2);
+ *   i == n:      the vote (0) or the weight (1, 2);   i == n + 1: the vote (1, 2);   beyond: +0;
+ *   a chunk whose vote is 0: zeros everywhere (0, 1) or the quiet NaN 0x7fc00000 everywhere (2)
+ * -- the bits those pack kernels write for an invalid client, and for a valid one for the weights g + scale * q.
+ * Errors: negative sizes, first or first_step, S not a positive multiple of 256, nclients outside 1..65535, an unknown
+ * layout, a null or misaligned image or out, a null global copy of a non-zero size, a stride below its element.      */
+int64_t mf_compress_chunk_bytes(int64_t S);
+int mf_compress_quantize(const void* x16, const void* g16, int64_t n16, const float* x32, const float* g32, int64_t n32,
+                         const float* e_in, float* e_out, const int* invalid_flag, float weight, int rounding,
+                         uint64_t seed, uint32_t round, uint32_t client, void* image, int64_t rank_stride, int64_t S,
+                         int world, void* stream);
+int mf_compress_decode(const void* image, int64_t chunk_stride, int nclients, int64_t S, int64_t first,
+                       int64_t first_step, const void* g16, int64_t n16, const float* g32, int64_t n32, int layout,
+                       float* out, int64_t out_stride, void* stream);
 int mf_nonfinite_flag(const void* x, int64_t n, int is16, int* flag, void* stream);
 
 /* ---- image transforms (data step before the path) ---------------------
