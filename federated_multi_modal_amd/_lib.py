@@ -60,12 +60,16 @@ SIGNATURES = {
     "mf_optimizer_step": [P, P, P, L, P, P, P, L, P, I, F, P, P, P, P, P, P],
     "mf_sgd_prox_step": [P, P, P, P, L, I, P, P, P],
     "mf_optimizer_step_prox": [P, P, P, L, P, P, P, L, P, I, F, P, P, P, P, P, P, P, P],
+    "mf_sgd_dyn_step": [P, P, P, P, P, L, I, P, P, P],
+    "mf_optimizer_step_dyn": [P, P, P, L, P, P, P, L, P, I, F, P, P, P, P, P, P, P, P, P],
     "mf_fedavg_pack_weighted": [P, L, P, L, P, F, P, P],
     "mf_fedavg_unpack_weighted": [P, P, L, P, L, P, P, P],
     "mf_fedavg_pack": [P, L, P, L, P, P, P],
     "mf_fedavg_unpack": [P, P, L, P, L, P, P, P],
     "mf_fedopt_step": [P, I, I, F, F, F, F, P, P, P, P, L, P, L, P, P, P],
     "mf_fedopt_deliver": [P, P, L, P, L, P, P, P],
+    "mf_feddyn_step": [P, F, I, P, P, P, P, L, P, L, P, P, P],
+    "mf_feddyn_deliver": [P, F, P, P, P, P, L, P, L, P, P, P],
     "mf_fedavg_reduce_ordered": [P, I, L, L, P, P],
     "mf_fedavg_reduce_trimmed": [P, I, L, L, I, L, P, P],
     "mf_fedavg_pack_robust": [P, L, P, L, P, P, P],

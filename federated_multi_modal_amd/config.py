@@ -216,6 +216,11 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # FedProx (Li et al.): mu * (w - w_global) added to every local step's clipped
                            # gradient; 0 = off (the plain SGD step)
                            PROX_MU=0.0,
+                           # FedDyn (Acar et al., ICLR 2021): alpha of the dynamic regulariser -- every local step
+                           # adds alpha * (w - w_global) - lambda_k, and the round's end updates each client's
+                           # lambda_k and the server's h in the kernel that unpacks the mean; 0 = off.  Not with
+                           # PROX_MU, SERVER_OPT, CLIENT_WEIGHTS, ROBUST_AGG, DP_CLIP or COMPRESS
+                           DYN_ALPHA=0.0,
                            # FedOpt server optimizer on the round's mean (federated.ServerOptimizer): "none" (the
                            # reference: the mean becomes the global model), "fedavgm" (Hsu et al.), "fedadagrad",
                            # "fedadam", "fedyogi" (Reddi et al.); eta, beta1, beta2 and tau of those papers

@@ -11,6 +11,7 @@
 // Rounding points follow torch: per-tensor norms in the grad's dtype (fp16 norm for fp16 grads),
 // total norm in fp32, coef = clamp(1/(total+1e-6), max 1); g = T(g*coef); d_p = T(g + wd*p);
 // buf = d_p (first step) or T(T(buf*mom) + d_p); p = T(p - lr*buf).
+#include <cstdio>
 #include <type_traits>
 #include <utility>
 
@@ -167,19 +168,35 @@ __global__ __launch_bounds__(1024) void clip_coef_kernel(const float* __restrict
 // gradient); d = T(p - pglob); gp = T(gc + mu*d); d_p = T(gp + wd*p); momentum and parameter update as the plain
 // step.  pglob is read only and must not overlap p, g or buf.
 //
-// The plain and the proximal step are the two instantiations of one element function, one scalar kernel, one
-// 8-wide body and one fused kernel, so each rounding is written once.  PROX = false reads neither pglob (null)
-// nor hyper[5] (the plain callers' hyper has 5 floats).
-template <typename T, bool PROX>
-MF_DEV void sgd_elem(float pe, float ge, float be, float qe, float coef, float lr, float momentum, float wd,
+// FedDyn (Acar et al., "Federated Learning Based on Dynamic Regularization", ICLR 2021): the local objective gains
+// -<lam, w> + (alpha/2) * ||w - w_global||^2, so the proximal line (alpha in mu's slot, hyper[5]) is followed by
+// gl = T(gp - lam): lam is the client's fp32 linear correction (read only, n elements in the buffer's order, whatever
+// T is), the difference one fp32 subtraction rounded to T.
+//
+// The plain, the proximal and the dynamic step are the three instantiations of one element function, one scalar
+// kernel, one 8-wide body and one fused kernel, so each rounding is written once.  SGD_PLAIN reads neither pglob
+// (null) nor hyper[5] (the plain callers' hyper has 5 floats); lam (null otherwise) is read by SGD_DYN alone.
+enum { SGD_PLAIN = 0, SGD_PROX = 1, SGD_DYN = 2 };
+
+// fp32 difference of a and b, materialised as fp32 before any fp16 rounding of it, as mul32 materialises a product:
+// fp16(a - b) with an fp32 b must not become one mixed-precision operation that rounds the exact difference once
+MF_DEV float sub32(float a, float b) {
+  float d = a - b;
+  asm volatile("" : "+v"(d));
+  return d;
+}
+
+template <typename T, int MODE>
+MF_DEV void sgd_elem(float pe, float ge, float be, float qe, float le, float coef, float lr, float momentum, float wd,
                      float mu, bool first, float& p_out, float& g_out, float& b_out) {
   const float gc = (float)(T)mul32(ge, coef);
   g_out = gc;
   float gp = gc;
-  if constexpr (PROX) {
+  if constexpr (MODE != SGD_PLAIN) {
     const float d = (float)(T)(pe - qe);
     gp = (float)(T)(gc + mul32(mu, d));
   }
+  if constexpr (MODE == SGD_DYN) gp = (float)(T)sub32(gp, le);
   const float dp = (float)(T)(gp + wd * pe);
   float b;
   if (first)
@@ -190,38 +207,44 @@ MF_DEV void sgd_elem(float pe, float ge, float be, float qe, float coef, float l
   p_out = (float)(T)(pe + (-lr) * b);
 }
 
-template <typename T, bool PROX>
+template <typename T, int MODE>
 __global__ void sgd_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
-                           int64_t n, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
+                           const float* __restrict__ lam, int64_t n, const float* __restrict__ coef_ptr,
+                           const float* __restrict__ hyper) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || hyper[4] != 0.f) return;
   const bool first = hyper[3] != 0.f;
-  float qe = 0.f, po, go, bo;
-  if constexpr (PROX) qe = (float)pglob[i];
-  sgd_elem<T, PROX>((float)p[i], (float)g[i], first ? 0.f : (float)buf[i], qe, coef_ptr[1], hyper[0], hyper[1],
-                    hyper[2], PROX ? hyper[5] : 0.f, first, po, go, bo);
+  float qe = 0.f, le = 0.f, po, go, bo;
+  if constexpr (MODE != SGD_PLAIN) qe = (float)pglob[i];
+  if constexpr (MODE == SGD_DYN) le = lam[i];
+  sgd_elem<T, MODE>((float)p[i], (float)g[i], first ? 0.f : (float)buf[i], qe, le, coef_ptr[1], hyper[0], hyper[1],
+                    hyper[2], MODE != SGD_PLAIN ? hyper[5] : 0.f, first, po, go, bo);
   g[i] = (T)go;
   buf[i] = (T)bo;
   p[i] = (T)po;
 }
 
 // sgd_kernel on 8 consecutive elements per thread (16-byte fp16 / 2 x 16-byte fp32 accesses, the proximal step one
-// more read of the global copy), the same per-element arithmetic; n % 8 == 0 and 32-byte aligned buffers
-template <typename T, bool PROX>
+// more read of the global copy, the dynamic one 32 bytes of lam besides), the same per-element arithmetic; n % 8 == 0
+// and 32-byte aligned buffers
+template <typename T, int MODE>
 MF_DEV void sgd8_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
-                      int64_t n8, int64_t i, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
+                      const float* __restrict__ lam, int64_t n8, int64_t i, const float* __restrict__ coef_ptr,
+                      const float* __restrict__ hyper) {
   using V = vec8<T>;
   if (i >= n8 || hyper[4] != 0.f) return;
   const float coef = coef_ptr[1];
-  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], mu = PROX ? hyper[5] : 0.f;
+  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], mu = MODE != SGD_PLAIN ? hyper[5] : 0.f;
   const bool first = hyper[3] != 0.f;
   V pv = ((V*)p)[i], gv = ((V*)g)[i], bv = first ? V{} : ((V*)buf)[i], qv{};
-  if constexpr (PROX) qv = ((const V*)pglob)[i];
+  f32x8 lv{};
+  if constexpr (MODE != SGD_PLAIN) qv = ((const V*)pglob)[i];
+  if constexpr (MODE == SGD_DYN) lv = ((const f32x8*)lam)[i];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     float po, go, bo;
-    sgd_elem<T, PROX>((float)pv[e], (float)gv[e], (float)bv[e], (float)qv[e], coef, lr, momentum, wd, mu, first, po,
-                      go, bo);
+    sgd_elem<T, MODE>((float)pv[e], (float)gv[e], (float)bv[e], (float)qv[e], lv[e], coef, lr, momentum, wd, mu, first,
+                      po, go, bo);
     gv[e] = (T)go;
     bv[e] = (T)bo;
     pv[e] = (T)po;
@@ -231,23 +254,26 @@ MF_DEV void sgd8_body(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf,
   ((V*)p)[i] = pv;
 }
 
-template <typename T, bool PROX>
+template <typename T, int MODE>
 __global__ void sgd8_kernel(T* __restrict__ p, T* __restrict__ g, T* __restrict__ buf, const T* __restrict__ pglob,
-                            int64_t n8, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
-  sgd8_body<T, PROX>(p, g, buf, pglob, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+                            const float* __restrict__ lam, int64_t n8, const float* __restrict__ coef_ptr,
+                            const float* __restrict__ hyper) {
+  sgd8_body<T, MODE>(p, g, buf, pglob, lam, n8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
 }
 
-// both flat buffers' SGD in one launch: blocks [0, nb16) update the fp16 trainables, the rest the fp32 ones
-template <bool PROX>
+// both flat buffers' SGD in one launch: blocks [0, nb16) update the fp16 trainables, the rest the fp32 ones; lam16 /
+// lam32 are lam and lam + n16
+template <int MODE>
 __global__ void sgd8_both_kernel(f16* __restrict__ p16, f16* __restrict__ g16, f16* __restrict__ b16,
-                                 const f16* __restrict__ q16, int64_t n16_8, float* __restrict__ p32,
-                                 float* __restrict__ g32, float* __restrict__ b32, const float* __restrict__ q32,
-                                 int64_t n32_8, unsigned nb16, const float* __restrict__ coef_ptr,
-                                 const float* __restrict__ hyper) {
+                                 const f16* __restrict__ q16, const float* __restrict__ lam16, int64_t n16_8,
+                                 float* __restrict__ p32, float* __restrict__ g32, float* __restrict__ b32,
+                                 const float* __restrict__ q32, const float* __restrict__ lam32, int64_t n32_8,
+                                 unsigned nb16, const float* __restrict__ coef_ptr, const float* __restrict__ hyper) {
   if (blockIdx.x < nb16)
-    sgd8_body<f16, PROX>(p16, g16, b16, q16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr, hyper);
+    sgd8_body<f16, MODE>(p16, g16, b16, q16, lam16, n16_8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, coef_ptr,
+                         hyper);
   else
-    sgd8_body<float, PROX>(p32, g32, b32, q32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x,
+    sgd8_body<float, MODE>(p32, g32, b32, q32, lam32, n32_8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x,
                            coef_ptr, hyper);
 }
 
@@ -482,6 +508,108 @@ __global__ void fedopt8_deliver_kernel(const float* __restrict__ x, f16* __restr
     deliver8_body<float>(x + n16, p32, g32, n32 / 8, (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x);
 }
 
+// FedDyn's round end (Acar et al., ICLR 2021, Algorithm 1) in unpack_kernel's place on the plain bucket [sum | votes].
+// Per element, with w the client's local weight and q the round's starting weight (its global copy), both read before
+// anything is written, every binary operation one fp32 operation (the file's contract(off)):
+//   client (flag[0] == 0):  lam = lam - alpha * (w - q)             the client's gradient estimate at its optimum
+//   server (STEP):          mean = sum / votes;  h = h - af * (mean - q),  af = alpha * (votes / N)
+//   both:                   x = mean - h / alpha;  val = fp16(x) delivered as unpack_kernel delivers the mean
+// h is the mean of the N clients' lam by construction: an absent client keeps its lam and reaches h through votes / N.
+// STEP = false (the rank's second and later clients) reads the stepped h and the same bucket, so it recomputes the
+// same x: no fp32 copy of x is kept.  No votes: the client goes back to its global copy, h and lam keep their bits.
+struct DynRound {
+  float alpha, af, votes;
+  bool take;  // this client took part: its lam is updated
+};
+
+template <bool STEP>
+MF_DEV DynRound dyn_round(const float* __restrict__ bucket, int64_t n, float alpha, int num_clients,
+                          const int* __restrict__ flag) {
+  const float votes = bucket[n];
+  float af = 0.f;
+  if constexpr (STEP) {
+    const float frac = votes / (float)num_clients;
+    af = alpha * frac;
+  }
+  return {alpha, af, votes, flag[0] == 0};
+}
+
+template <bool STEP>
+MF_DEV float feddyn_elem(const DynRound& r, float sum, float w, float q, float& h, float& lam) {
+  if (r.take) {
+    const float d = w - q;
+    const float ad = r.alpha * d;
+    lam = lam - ad;
+  }
+  const float mean = sum / r.votes;
+  if constexpr (STEP) {
+    const float dm = mean - q;
+    const float t = r.af * dm;
+    h = h - t;
+  }
+  const float hq = h / r.alpha;
+  return mean - hq;
+}
+
+// one element per thread over [fp16 trainables | fp32 trainables]
+template <bool STEP>
+__global__ void feddyn_kernel(const float* __restrict__ bucket, float alpha, int num_clients, float* __restrict__ h,
+                              float* __restrict__ lam, const int* __restrict__ flag, f16* __restrict__ p16,
+                              int64_t n16, float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
+                              float* __restrict__ g32) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n = n16 + n32;
+  if (i >= n) return;
+  const DynRound r = dyn_round<STEP>(bucket, n, alpha, num_clients, flag);
+  if (r.votes == 0.f) return restore(i, p16, n16, p32, g16, g32);
+  const float w = i < n16 ? (float)p16[i] : p32[i - n16], q = i < n16 ? (float)g16[i] : g32[i - n16];
+  float he = h[i], le = r.take ? lam[i] : 0.f;
+  const float x = feddyn_elem<STEP>(r, bucket[i], w, q, he, le);
+  if (r.take) lam[i] = le;
+  if constexpr (STEP) h[i] = he;
+  deliver((f16)x, i, p16, n16, p32, g16, g32);
+}
+
+// feddyn_kernel on 8 consecutive elements per thread of one buffer, as fedopt8_body: bucket, h, lam already offset
+// to this buffer's part; n % 8 == 0 and aligned pointers (the launcher checks)
+template <typename T, bool STEP>
+MF_DEV void feddyn8_body(const float* __restrict__ bucket, const DynRound& r, float* __restrict__ h,
+                         float* __restrict__ lam, T* __restrict__ p, T* __restrict__ g, int64_t n8, int64_t i) {
+  if (i >= n8) return;
+  const vec8<T> gv = ((const vec8<T>*)g)[i];
+  if (r.votes == 0.f) {
+    ((vec8<T>*)p)[i] = gv;
+    return;
+  }
+  const vec8<T> pv = ((const vec8<T>*)p)[i];
+  const f32x8 sv = ((const f32x8*)bucket)[i];
+  f32x8 hv = ((f32x8*)h)[i], lv = r.take ? ((f32x8*)lam)[i] : f32x8{}, xv;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float he = hv[e], le = lv[e];
+    xv[e] = feddyn_elem<STEP>(r, sv[e], (float)pv[e], (float)gv[e], he, le);
+    hv[e] = he;
+    lv[e] = le;
+  }
+  if (r.take) ((f32x8*)lam)[i] = lv;
+  if constexpr (STEP) ((f32x8*)h)[i] = hv;
+  deliver8<T>(xv, p, g, i);
+}
+
+// both flat buffers in one launch, split as fedopt8_step_kernel splits them: blocks [0, nb16) the fp16 trainables
+template <bool STEP>
+__global__ void feddyn8_kernel(const float* __restrict__ bucket, float alpha, int num_clients, float* __restrict__ h,
+                               float* __restrict__ lam, const int* __restrict__ flag, f16* __restrict__ p16,
+                               int64_t n16, float* __restrict__ p32, int64_t n32, f16* __restrict__ g16,
+                               float* __restrict__ g32, unsigned nb16) {
+  const DynRound r = dyn_round<STEP>(bucket, n16 + n32, alpha, num_clients, flag);
+  if (blockIdx.x < nb16)
+    feddyn8_body<f16, STEP>(bucket, r, h, lam, p16, g16, n16 / 8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+  else
+    feddyn8_body<float, STEP>(bucket + n16, r, h + n16, lam + n16, p32, g32, n32 / 8,
+                              (int64_t)(blockIdx.x - nb16) * blockDim.x + threadIdx.x);
+}
+
 // out[i] = (((g_0[i] + g_1[i]) + g_2[i]) + ...) in client order, g_c = gathered + c * stride: the
 // per-key torch.stack(...) sum of trainers/maple_fed.py:311-314 in the order the reference stacks its
 // clients, whatever order the collective delivered them in (8 floats per thread, fp32 accumulation)
@@ -671,50 +799,58 @@ int clip_launches(const void* g16, const float* g32, const void* chunks, int nch
   return 0;
 }
 
-// SGD over one flat buffer: 8 elements per thread when the size and every pointer allow (a null pglob does), one
-// element per thread otherwise
-template <bool PROX>
-int sgd_step(void* p, void* g, void* buf, const void* pglob, int64_t n, int is16, const float* coef,
+// SGD over one flat buffer: 8 elements per thread when the size and every pointer allow (a null pglob or lam does),
+// one element per thread otherwise
+template <int MODE>
+int sgd_step(void* p, void* g, void* buf, const void* pglob, const float* lam, int64_t n, int is16, const float* coef,
              const float* hyper, hipStream_t st) {
   if (n <= 0) return 0;
-  const bool vec = n % 8 == 0 && aligned(p, 32) && aligned(g, 32) && aligned(buf, 32) && aligned(pglob, 32);
+  const bool vec = n % 8 == 0 && aligned(p, 32) && aligned(g, 32) && aligned(buf, 32) && aligned(pglob, 32) &&
+                   aligned(lam, 32);
   if (vec && is16)
-    sgd8_kernel<f16, PROX><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n / 8, coef,
-                                                        hyper);
+    sgd8_kernel<f16, MODE><<<nblk(n / 8), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, lam, n / 8,
+                                                        coef, hyper);
   else if (vec)
-    sgd8_kernel<float, PROX><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob,
+    sgd8_kernel<float, MODE><<<nblk(n / 8), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, lam,
                                                           n / 8, coef, hyper);
   else if (is16)
-    sgd_kernel<f16, PROX><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, n, coef, hyper);
+    sgd_kernel<f16, MODE><<<nblk(n), 256, 0, st>>>((f16*)p, (f16*)g, (f16*)buf, (const f16*)pglob, lam, n, coef,
+                                                   hyper);
   else
-    sgd_kernel<float, PROX><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, n, coef,
-                                                     hyper);
+    sgd_kernel<float, MODE><<<nblk(n), 256, 0, st>>>((float*)p, (float*)g, (float*)buf, (const float*)pglob, lam, n,
+                                                     coef, hyper);
   MF_CHECK_LAUNCH();
   return 0;
 }
 
 // The whole optimizer step in three launches: clip_launches (the latch replaces the two torch.maximum launches the
 // engine used to make, at the step's start for the input check and here for the loss), then SGD over the fp16 and the
-// fp32 flat buffers in one launch.  Bit-identical to mf_clip_grad_norm + two mf_sgd_step (PROX: mf_sgd_prox_step; the
-// clip norm is the model gradient's, without the proximal term).
-template <bool PROX>
+// fp32 flat buffers in one launch.  Bit-identical to mf_clip_grad_norm + two mf_sgd_step (SGD_PROX: mf_sgd_prox_step,
+// SGD_DYN: mf_sgd_dyn_step; the clip norm is the model gradient's, without the proximal and the linear term).  lam
+// (SGD_DYN; null otherwise) covers both buffers, [fp16 trainables | fp32 trainables]: lam + n16 is 32-byte aligned
+// exactly when lam is and n16 % 8 == 0.
+template <int MODE>
 int optimizer_step(void* p16, void* g16, void* b16, const void* glob16, int64_t n16, float* p32, float* g32,
-                   float* b32, const float* glob32, int64_t n32, const void* chunks, int nchunks, float max_norm,
-                   float* part, float* out, float* hyper, const float* halt_src, const int* input_flag,
-                   hipStream_t st) {
+                   float* b32, const float* glob32, int64_t n32, const float* lam, const void* chunks, int nchunks,
+                   float max_norm, float* part, float* out, float* hyper, const float* halt_src,
+                   const int* input_flag, hipStream_t st) {
   int rc = clip_launches(g16, g32, chunks, nchunks, max_norm, part, out, hyper, halt_src, input_flag, st);
   if (rc) return rc;
-  const bool vec16 = n16 % 8 == 0 && aligned(p16, 32) && aligned(g16, 32) && aligned(b16, 32) && aligned(glob16, 32);
-  const bool vec32 = n32 % 8 == 0 && aligned(p32, 32) && aligned(g32, 32) && aligned(b32, 32) && aligned(glob32, 32);
+  const float* lam32 = lam ? lam + n16 : nullptr;
+  const bool vec16 = n16 % 8 == 0 && aligned(p16, 32) && aligned(g16, 32) && aligned(b16, 32) &&
+                     aligned(glob16, 32) && aligned(lam, 32);
+  const bool vec32 = n32 % 8 == 0 && aligned(p32, 32) && aligned(g32, 32) && aligned(b32, 32) &&
+                     aligned(glob32, 32) && aligned(lam32, 32);
   if (vec16 && vec32 && n16 + n32 > 0) {
     const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
-    sgd8_both_kernel<PROX><<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, (const f16*)glob16, n16 / 8,
-                                                        p32, g32, b32, glob32, n32 / 8, nb16, out, hyper);
+    sgd8_both_kernel<MODE><<<nb16 + nb32, 256, 0, st>>>((f16*)p16, (f16*)g16, (f16*)b16, (const f16*)glob16, lam,
+                                                        n16 / 8, p32, g32, b32, glob32, lam32, n32 / 8, nb16, out,
+                                                        hyper);
     MF_CHECK_LAUNCH();
     return 0;
   }
-  rc = sgd_step<PROX>(p16, g16, b16, glob16, n16, 1, out, hyper, st);
-  return rc ? rc : sgd_step<PROX>(p32, g32, b32, glob32, n32, 0, out, hyper, st);
+  rc = sgd_step<MODE>(p16, g16, b16, glob16, lam, n16, 1, out, hyper, st);
+  return rc ? rc : sgd_step<MODE>(p32, g32, b32, glob32, lam32, n32, 0, out, hyper, st);
 }
 
 template <bool WEIGHTED>
@@ -742,7 +878,7 @@ extern "C" int mf_clip_grad_norm(const void* g16, const float* g32, const void* 
 
 extern "C" int mf_sgd_step(void* p, void* g, void* buf, int64_t n, int is16, const float* coef, const float* hyper,
                            void* stream) {
-  return sgd_step<false>(p, g, buf, nullptr, n, is16, coef, hyper, (hipStream_t)stream);
+  return sgd_step<SGD_PLAIN>(p, g, buf, nullptr, nullptr, n, is16, coef, hyper, (hipStream_t)stream);
 }
 
 // mf_sgd_step with the FedProx term mu * (p - pglob), mu = hyper[5] (a 6-float hyper)
@@ -750,14 +886,23 @@ extern "C" int mf_sgd_prox_step(void* p, void* g, void* buf, const void* pglob, 
                                 const float* hyper, void* stream) {
   if (n <= 0) return 0;
   if (!pglob) return mf_set_error("mf_sgd_prox_step: no global copy", -1);
-  return sgd_step<true>(p, g, buf, pglob, n, is16, coef, hyper, (hipStream_t)stream);
+  return sgd_step<SGD_PROX>(p, g, buf, pglob, nullptr, n, is16, coef, hyper, (hipStream_t)stream);
+}
+
+// mf_sgd_prox_step with FedDyn's linear term: alpha = hyper[5] in mu's place, then lam (n fp32 elements) subtracted
+extern "C" int mf_sgd_dyn_step(void* p, void* g, void* buf, const void* pglob, const float* lam, int64_t n, int is16,
+                               const float* coef, const float* hyper, void* stream) {
+  if (n <= 0) return 0;
+  if (!pglob) return mf_set_error("mf_sgd_dyn_step: no global copy", -1);
+  if (!lam) return mf_set_error("mf_sgd_dyn_step: no lam", -1);
+  return sgd_step<SGD_DYN>(p, g, buf, pglob, lam, n, is16, coef, hyper, (hipStream_t)stream);
 }
 
 extern "C" int mf_optimizer_step(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
                                  int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
                                  float* hyper, const float* halt_src, const int* input_flag, void* stream) {
-  return optimizer_step<false>(p16, g16, b16, nullptr, n16, p32, g32, b32, nullptr, n32, chunks, nchunks, max_norm,
-                               part, out, hyper, halt_src, input_flag, (hipStream_t)stream);
+  return optimizer_step<SGD_PLAIN>(p16, g16, b16, nullptr, n16, p32, g32, b32, nullptr, n32, nullptr, chunks, nchunks,
+                                   max_norm, part, out, hyper, halt_src, input_flag, (hipStream_t)stream);
 }
 
 // mf_optimizer_step with the proximal SGD launch
@@ -766,8 +911,19 @@ extern "C" int mf_optimizer_step_prox(void* p16, void* g16, void* b16, int64_t n
                                       float* out, float* hyper, const float* halt_src, const int* input_flag,
                                       const void* glob16, const float* glob32, void* stream) {
   if ((n16 > 0 && !glob16) || (n32 > 0 && !glob32)) return mf_set_error("mf_optimizer_step_prox: no global copy", -1);
-  return optimizer_step<true>(p16, g16, b16, glob16, n16, p32, g32, b32, glob32, n32, chunks, nchunks, max_norm, part,
-                              out, hyper, halt_src, input_flag, (hipStream_t)stream);
+  return optimizer_step<SGD_PROX>(p16, g16, b16, glob16, n16, p32, g32, b32, glob32, n32, nullptr, chunks, nchunks,
+                                  max_norm, part, out, hyper, halt_src, input_flag, (hipStream_t)stream);
+}
+
+// mf_optimizer_step_prox with the dynamic SGD launch: lam, n16 + n32 fp32 elements in the bucket's order
+extern "C" int mf_optimizer_step_dyn(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
+                                     int64_t n32, const void* chunks, int nchunks, float max_norm, float* part,
+                                     float* out, float* hyper, const float* halt_src, const int* input_flag,
+                                     const void* glob16, const float* glob32, const float* lam, void* stream) {
+  if ((n16 > 0 && !glob16) || (n32 > 0 && !glob32)) return mf_set_error("mf_optimizer_step_dyn: no global copy", -1);
+  if (n16 + n32 > 0 && !lam) return mf_set_error("mf_optimizer_step_dyn: no lam", -1);
+  return optimizer_step<SGD_DYN>(p16, g16, b16, glob16, n16, p32, g32, b32, glob32, n32, lam, chunks, nchunks, max_norm,
+                                 part, out, hyper, halt_src, input_flag, (hipStream_t)stream);
 }
 
 extern "C" int mf_fedavg_pack(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
@@ -851,6 +1007,58 @@ extern "C" int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* 
   }
   MF_CHECK_LAUNCH();
   return 0;
+}
+
+namespace {
+
+// the checks and the launch mf_feddyn_step and mf_feddyn_deliver share; launch shape as mf_fedopt_step's
+template <bool STEP>
+int feddyn_launch(const char* who, const float* bucket, float alpha, int num_clients, float* h, float* lam,
+                  const int* flag, void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
+                  hipStream_t st) {
+  char msg[96];
+  const auto fail = [&](const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return mf_set_error(msg, -1);
+  };
+  if (n16 < 0 || n32 < 0) return fail("negative size");
+  if (!__builtin_isfinite(alpha) || !(alpha > 0.f)) return fail("alpha not finite and > 0");
+  if (num_clients < 1) return fail("num_clients < 1");
+  if (!h || !lam || !flag) return fail("null h, lam or flag");
+  if (n16 + n32 == 0) return 0;
+  if (!bucket || (n16 > 0 && (!p16 || !g16)) || (n32 > 0 && (!p32 || !g32)))
+    return fail("null bucket, weights or global copy");
+  const bool vec = n16 % 8 == 0 && n32 % 8 == 0 && aligned(bucket, 32) && aligned(h, 32) && aligned(lam, 32) &&
+                   aligned(p16, 16) && aligned(g16, 16) && aligned(p32, 32) && aligned(g32, 32);
+  if (vec) {
+    const unsigned nb16 = nblk(n16 / 8), nb32 = nblk(n32 / 8);
+    feddyn8_kernel<STEP><<<nb16 + nb32, 256, 0, st>>>(bucket, alpha, num_clients, h, lam, flag, (f16*)p16, n16, p32,
+                                                      n32, (f16*)g16, g32, nb16);
+  } else {
+    feddyn_kernel<STEP><<<nblk(n16 + n32), 256, 0, st>>>(bucket, alpha, num_clients, h, lam, flag, (f16*)p16, n16, p32,
+                                                         n32, (f16*)g16, g32);
+  }
+  MF_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+// FedDyn's round end on the summed plain bucket [sum | votes]: the server's h steps, this client's lam updates (unless
+// *flag) and x = mean - h / alpha is delivered as fp16 into its weights and global copy
+extern "C" int mf_feddyn_step(const float* bucket, float alpha, int num_clients, float* h, float* lam, const int* flag,
+                              void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32, void* stream) {
+  return feddyn_launch<true>("mf_feddyn_step", bucket, alpha, num_clients, h, lam, flag, p16, n16, p32, n32, g16, g32,
+                             (hipStream_t)stream);
+}
+
+// ... for the rank's second and later clients: the stepped h is only read, the same x recomputed, this client's own lam
+// updated from its own weights and global copy
+extern "C" int mf_feddyn_deliver(const float* bucket, float alpha, const float* h, float* lam, const int* flag,
+                                 void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
+                                 void* stream) {
+  return feddyn_launch<false>("mf_feddyn_deliver", bucket, alpha, 1, (float*)h, lam, flag, p16, n16, p32, n32, g16,
+                              g32, (hipStream_t)stream);
 }
 
 extern "C" int mf_fedavg_reduce_ordered(const float* gathered, int nclients, int64_t stride, int64_t n, float* out,

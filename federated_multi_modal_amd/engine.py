@@ -613,11 +613,13 @@ class MapleEngine:
             self._table_owner = self
             self._build_text_constants()
             # {lr, momentum, weight_decay, first_step, halt, mu}: read by the SGD kernels from device memory (mu: the
-            # FedProx coefficient, read by the proximal step only -- set_proximal)
+            # FedProx coefficient, read by the proximal step only -- set_proximal; FedDyn's alpha sits in the same slot,
+            # read by the dynamic step only -- set_dynamic)
             self.hyper = torch.tensor([0.0, cfg.momentum, cfg.weight_decay, 1.0, 0.0, 0.0], device=self.device,
                                       dtype=F32)
-            # set_proximal's state, one dict shared with every engine built on these parameters (shared=)
-            self._prox = {"glob": None, "captured": False}
+            # set_proximal's and set_dynamic's state, one dict shared with every engine built on these parameters
+            # (shared=); "lam" is FedDyn's correction and selects the dynamic launch
+            self._prox = {"glob": None, "captured": False, "lam": None}
         else:
             assert shared.K == self.K and shared.J == self.J and shared.device == self.device
             assert shared.cfg.eot_truncate == cfg.eot_truncate
@@ -1090,13 +1092,42 @@ class MapleEngine:
         if self._prox["captured"]:
             raise RuntimeError("set_proximal after a training step was captured: the captured graph holds the "
                                "plain SGD launch; call it before the first capture_train_step()")
+        if self._prox["lam"] is not None:
+            raise ValueError("set_proximal after set_dynamic: FedDyn's alpha and FedProx's mu share hyper[5], and the "
+                             "dynamic step already holds the proximal term")
+        self._check_global_copies(glob16, glob32)
+        self._prox["glob"] = (glob16, glob32)
+        self.set_prox_mu(mu)
+
+    def _check_global_copies(self, glob16: torch.Tensor, glob32: torch.Tensor):
         for name, t, ref in (("glob16", glob16, self.flat16), ("glob32", glob32, self.flat32)):
             if (t.dtype != ref.dtype or t.device != ref.device or t.numel() != ref.numel() or not t.is_contiguous()
                     or (t.numel() and t.data_ptr() == ref.data_ptr())):
                 raise ValueError(f"{name}: a contiguous {ref.dtype} buffer of {ref.numel()} elements on {ref.device}, "
                                  "other than the trainables themselves, is required")
+
+    def set_dynamic(self, alpha: float, glob16: torch.Tensor, glob32: torch.Tensor, lam: torch.Tensor):
+        """FedDyn (Acar et al., ICLR 2021): every local step adds alpha * (w - w_global) - lam to the clipped gradient
+        (mf_optimizer_step_dyn).  glob16 / glob32 as set_proximal's; lam: the client's fp32 correction, n16 + n32
+        elements in the order [fp16 trainables | fp32 trainables] (FedAvgBucket.lam, updated in place at the round's
+        end).  The same pointer-lifetime contract as set_proximal: all three go into the captured step, stay alive and
+        in place, and this runs before any capture.  Not together with set_proximal."""
+        if self._prox["captured"]:
+            raise RuntimeError("set_dynamic after a training step was captured: the captured graph holds the "
+                               "plain SGD launch; call it before the first capture_train_step()")
+        if self._prox["glob"] is not None and self._prox["lam"] is None:
+            raise ValueError("set_dynamic after set_proximal: FedDyn's alpha and FedProx's mu share hyper[5], and the "
+                             "dynamic step already holds the proximal term")
+        alpha = float(alpha)
+        if not math.isfinite(alpha) or alpha <= 0.0:
+            raise ValueError(f"FedDyn alpha must be finite and > 0, got {alpha}")
+        self._check_global_copies(glob16, glob32)
+        n = self.n16 + self.n32
+        if (lam.dtype != F32 or lam.device != self.flat32.device or lam.numel() != n or not lam.is_contiguous()):
+            raise ValueError(f"lam: a contiguous fp32 buffer of {n} elements on {self.flat32.device} is required")
         self._prox["glob"] = (glob16, glob32)
-        self.set_prox_mu(mu)
+        self._prox["lam"] = lam
+        self.hyper[5] = alpha
 
     def set_prox_mu(self, mu: float):
         """The proximal coefficient, read from device memory by the (captured) step: change it between rounds
@@ -1123,10 +1154,15 @@ class MapleEngine:
             ops.optimizer_step(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32,
                                self.chunks, self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out,
                                self.hyper, self.loss_out[3:4], self.input_flag)
-        else:  # FedProx: the same three launches, the SGD one reading the global copy too (set_proximal)
+        elif self._prox["lam"] is None:  # FedProx: the same three launches, the SGD one reading the global copy too
             ops.optimizer_step_prox(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32,
                                     self.chunks, self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out,
                                     self.hyper, self.loss_out[3:4], self.input_flag, glob[0], glob[1])
+        else:  # FedDyn: ... and the client's correction lam (set_dynamic)
+            ops.optimizer_step_dyn(self.flat16, self.gflat16, self.mom16, self.flat32, self.gflat32, self.mom32,
+                                   self.chunks, self.nchunks, self.cfg.max_grad_norm, self.norm_part, self.clip_out,
+                                   self.hyper, self.loss_out[3:4], self.input_flag, glob[0], glob[1],
+                                   self._prox["lam"])
         # the momentum buffers now exist (first_step -> 0) unless the update was skipped
         self.hyper[3:4].mul_(self.hyper[4:5])  # device ops, legal inside graph capture
 

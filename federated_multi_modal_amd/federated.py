@@ -116,6 +116,23 @@ round and only for a client that did not fail, so a late-failure re-pack reads t
 round, reproduces the same codes, and the residual is applied once; an invalid or failed client sends nothing (codes,
 scales and vote 0) and keeps its residual.  Not combined with dp_clip / dp_std: a quantised, fed-back update no longer
 has an L2 norm within the bound.
+
+FedDyn (FedAvgBucket dyn= / FedDynState; FED.DYN_ALPHA, off by default): the dynamic regularisation of Acar, Zhao, Matas
+Navarro, Mattina, Whatmough and Saligrama (ICLR 2021), which makes the clients' local optima agree with the global one
+where FedProx only pulls them towards the last global model.  Client k minimises L_k(w) - <lam_k, w> + (alpha / 2)
+||w - g||^2: the captured step's SGD launch reads the bucket's global copy, as under FedProx, and the client's fp32
+correction lam_k besides (engine.set_dynamic, mf_optimizer_step_dyn).  The round's end moves no extra byte -- the bucket,
+the exchange and the reduce are the plain ones -- and runs in the one kernel that would otherwise unpack the mean
+(mf_feddyn_step in mf_fedavg_unpack's place): lam_k = lam_k - alpha * (w_k - g) for a client that took part, the server's
+h = h - alpha * (m / N) * (mean - g) over the m voting of the N clients, and every client receives
+fp16(mean - h / alpha).  One FedDynState per process holds h, fp32 of the bucket's size, replicated as the FedOpt state
+is: every rank steps it on the same summed bucket with the same kernel.  The first unpack() after the rank's packs
+steps h and writes that client; the others (mf_feddyn_deliver) read the stepped h and the same bucket and so recompute
+the same weights, each updating its own lam_k: no fp32 copy of the model is kept.  An invalid, failed or late-failed
+client (the bucket's device flag) keeps its lam_k, the paper's rule for a device that did not take part, and its
+absence reaches h through m / N; a round without a valid client leaves h and every lam_k untouched.  h is the mean of
+the lam_k by construction only while the server sees the clients' own weights in a plain mean, so dyn is not combined
+with client weights, the robust aggregation, dp_clip, compress or a server optimizer; both exchange modes are allowed.
 """
 from __future__ import annotations
 
@@ -197,6 +214,8 @@ class _HipKernels:
     compress_chunk_bytes = staticmethod(ops.compress_chunk_bytes)
     compress_quantize = staticmethod(ops.compress_quantize)
     compress_decode = staticmethod(ops.compress_decode)
+    feddyn_step = staticmethod(ops.feddyn_step)
+    feddyn_deliver = staticmethod(ops.feddyn_deliver)
 
 
 SERVER_OPTS = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
@@ -271,6 +290,43 @@ class ServerOptimizer:
             getattr(self, k).copy_(sd[k].reshape(-1))
 
 
+class FedDynState:
+    """FedDyn's server state of one process, shared by the rank's buckets (module docstring): h, the mean of the
+    num_clients clients' corrections lam_k, fp32 zeros of n16 + n32 elements in the bucket's order until a round
+    completes.  Each bucket keeps its own lam_k."""
+
+    def __init__(self, alpha: float, engine, num_clients: int):
+        alpha = float(alpha)
+        if not math.isfinite(alpha) or alpha <= 0.0:
+            raise ValueError(f"FedDyn alpha {alpha}: finite and > 0")
+        if isinstance(num_clients, bool) or not isinstance(num_clients, int) or num_clients < 1:
+            raise ValueError(f"FedDyn num_clients {num_clients!r}: an integer >= 1")
+        self.alpha, self.num_clients = alpha, num_clients
+        # engine: what FedAvgBucket needs (n16, n32, flat16)
+        self.n16, self.n32 = engine.n16, engine.n32
+        self.h = torch.zeros(self.n16 + self.n32, device=engine.flat16.device, dtype=torch.float32)
+        self.pending = False  # a pack since the last step: the next unpack steps h, the others deliver
+
+    def reset(self):
+        self.h.zero_()
+
+    def state_dict(self) -> dict:
+        """CPU tensors and plain numbers only (torch.load(..., weights_only=True) reads it)."""
+        return {"alpha": self.alpha, "num_clients": self.num_clients, "n16": self.n16, "n32": self.n32,
+                "h": self.h.detach().cpu().clone()}
+
+    def load_state_dict(self, sd: dict):
+        """The h of a saved state; this state's own alpha and client count stay (they are the run's configuration).
+        ValueError for other sizes."""
+        if (sd.get("n16"), sd.get("n32")) != (self.n16, self.n32):
+            raise ValueError(f"FedDyn state of sizes {(sd.get('n16'), sd.get('n32'))}, this one has "
+                             f"{(self.n16, self.n32)}")
+        t = sd.get("h")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != self.n16 + self.n32:
+            raise ValueError(f"FedDyn state: 'h' is not fp32 of {self.n16 + self.n32} elements")
+        self.h.copy_(t.reshape(-1))
+
+
 def resolve_client_weights(spec, sample_counts: Sequence[int], num_clients: int) -> Optional[List[float]]:
     """FED.CLIENT_WEIGHTS -> one FedAvg weight per client, or None for the unweighted mean.
 
@@ -324,7 +380,9 @@ class FedAvgBucket:
     whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8") sends the update as int8 codes
     with block scales instead (module docstring): `compress_rounding` "nearest" | "stochastic", `error_feedback` keeps
     the rounding error as a per-client residual (state_dict() / load_state_dict() carry it), `compress_seed` and
-    `client`, the global client index, select the stochastic rounding's bits.
+    `client`, the global client index, select the stochastic rounding's bits.  `dyn` (the process's FedDynState) selects
+    FedDyn (module docstring): the bucket keeps its client's correction `lam` and unpack() runs the round's end; not with
+    weight, robust, dp_clip, compress or server.
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
@@ -334,7 +392,8 @@ class FedAvgBucket:
                  mode: str = "ordered", shard_single: bool = False, weight: Optional[float] = None,
                  server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1,
                  dp_clip: Optional[float] = None, compress: Optional[str] = None, compress_rounding: str = "nearest",
-                 error_feedback: bool = True, compress_seed: int = 0, client: int = 0):
+                 error_feedback: bool = True, compress_seed: int = 0, client: int = 0,
+                 dyn: Optional["FedDynState"] = None):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         if compress is not None and compress not in COMPRESS:
@@ -348,6 +407,15 @@ class FedAvgBucket:
         if compress is not None and dp_clip is not None:
             raise ValueError("FedAvg compress with dp_clip: a quantised, fed-back update no longer has an L2 norm "
                              "within the bound")
+        if dyn is not None:
+            for label, on in (("a client weight", weight is not None), ("robust aggregation", robust is not None),
+                              ("dp_clip", dp_clip is not None), ("compress", compress is not None),
+                              ("a server optimizer", server is not None)):
+                if on:
+                    raise ValueError(f"FedAvg dyn with {label}: FedDyn's h is the mean of the clients' corrections "
+                                     "only while the server sees the clients' own weights in a plain mean")
+            if (dyn.n16, dyn.n32) != (engine.n16, engine.n32):
+                raise ValueError("FedAvgBucket: the FedDyn state was built for other sizes")
         self.compress, self.compress_rounding, self.error_feedback = compress, compress_rounding, bool(error_feedback)
         self.compress_seed, self.client = compress_seed, client
         if dp_clip is not None:
@@ -409,6 +477,9 @@ class FedAvgBucket:
         if server is not None and (server.n16, server.n32) != (engine.n16, engine.n32):
             raise ValueError("FedAvgBucket: the server optimizer was built for other sizes")
         self.server = server
+        # FedDyn: this client's correction lam_k, updated in place by unpack() (the captured step holds its pointer)
+        self.dyn = dyn
+        self.lam = None if dyn is None else torch.zeros(n, device=dev, dtype=torch.float32)
 
     # -- per client
     def pack(self, failed: bool = False):
@@ -450,16 +521,28 @@ class FedAvgBucket:
             self.k.fedavg_pack_weighted(e.flat16, e.flat32, self.flag, self.weight, self.buf)
         if self.server is not None:
             self.server.pending = True  # a new exchange: its first unpack applies the server step
+        if self.dyn is not None:
+            self.dyn.pending = True  # ... steps h
 
     def unpack(self):
         """The fp16-rounded mean into every trainable (device-side n_valid; n_valid == 0 leaves the weights
         at the previous global copy).  No host synchronisation.  With a server optimizer: the first unpack after
         the rank's packs applies the server step to the summed bucket and writes this client; the other local
         clients receive the same fp16(x) (deliver), so the step runs once per exchange -- a late-failure
-        re-exchange packs again before any unpack and changes nothing about that."""
+        re-exchange packs again before any unpack and changes nothing about that.  With dyn the same holds for FedDyn's
+        round end: the first unpack steps h, the others deliver, each updates its own lam unless its flag is set."""
         e = self.e
         sv = self.server
-        if sv is not None:
+        dyn = self.dyn
+        if dyn is not None:
+            if dyn.pending:
+                self.k.feddyn_step(self.buf, dyn.alpha, dyn.num_clients, dyn.h, self.lam, self.flag, e.flat16,
+                                   e.flat32, self.global16, self.global32)
+                dyn.pending = False
+            else:
+                self.k.feddyn_deliver(self.buf, dyn.alpha, dyn.h, self.lam, self.flag, e.flat16, e.flat32,
+                                      self.global16, self.global32)
+        elif sv is not None:
             if sv.pending:
                 self.k.fedopt_step(self.buf, self.weighted, sv.name, sv.beta1, sv.beta2, sv.tau, sv.lr,
                                    sv.x, sv.m, sv.v, e.flat16, e.flat32, self.global16, self.global32)
@@ -482,6 +565,9 @@ class FedAvgBucket:
         self.global32.copy_(self.e.flat32)
         if self.server is not None:
             self.server.reset_from(self)
+        if self.dyn is not None:  # weights from outside the round loop: the corrections restart, h stays their mean
+            self.lam.zero_()
+            self.dyn.reset()
 
     def n_valid(self) -> int:
         """Valid clients of the last round (host sync)."""
@@ -496,12 +582,27 @@ class FedAvgBucket:
         return norm, scale
 
     def state_dict(self) -> dict:
-        """The error-feedback residual as a CPU fp32 tensor (None without one); torch.load(..., weights_only=True)
-        reads it."""
-        return {"residual": None if self.resid is None else self.resid.detach().cpu().clone()}
+        """The error-feedback residual as a CPU fp32 tensor (None without one) and, under FedDyn, the correction lam
+        next to it; torch.load(..., weights_only=True) reads it."""
+        sd = {"residual": None if self.resid is None else self.resid.detach().cpu().clone()}
+        if self.lam is not None:
+            sd["lam"] = self.lam.detach().cpu().clone()
+        return sd
 
     def load_state_dict(self, sd: dict):
-        """A saved residual.  ValueError when this bucket keeps none, or for another size or dtype."""
+        """A saved residual and lam (an absent or None entry zeroes this bucket's).  ValueError when this bucket keeps
+        none, or for another size or dtype."""
+        lam = sd.get("lam")
+        if lam is not None:
+            if self.lam is None:
+                raise ValueError("FedAvgBucket state: a lam for a bucket without FedDyn")
+            if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or lam.numel() != self.lam.numel():
+                raise ValueError(f"FedAvgBucket state: lam is not fp32 of {self.lam.numel()} elements")
+        if self.lam is not None:
+            if lam is None:
+                self.lam.zero_()
+            else:
+                self.lam.copy_(lam.reshape(-1))
         t = sd.get("residual")
         if t is None:
             if self.resid is not None:

@@ -660,18 +660,22 @@ def clip_grad_norm(g16, g32, chunks, nchunks, max_norm, part, out):
     _rec(ev)
 
 
-def _sgd_call(name, p, g, buf, coef, hyper, *pglob):
-    # p, g, momentum read; p, momentum written (each at the parameter's element size); sgd_prox_step also reads pglob
+def _sgd_call(name, p, g, buf, coef, hyper, *extra):
+    # p, g, momentum read; p, momentum written (each at the parameter's element size); sgd_prox_step also reads pglob,
+    # sgd_dyn_step pglob and the fp32 lam
     is16 = p.dtype == torch.float16
-    ev = _hbm(f"{name}/{'f16' if is16 else 'f32'}", p.numel() * (5.0 + len(pglob)) * p.element_size())
-    call("mf_" + name, _p(p), _p(g), _p(buf), *map(_p, pglob), p.numel(), int(is16), _p(coef), _p(hyper), _s())
+    ev = _hbm(f"{name}/{'f16' if is16 else 'f32'}",
+              p.numel() * 5.0 * p.element_size() + sum(float(t.numel() * t.element_size()) for t in extra))
+    call("mf_" + name, _p(p), _p(g), _p(buf), *map(_p, extra), p.numel(), int(is16), _p(coef), _p(hyper), _s())
     _rec(ev)
 
 
 def _optimizer_call(name, p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
                     input_flag, *glob):
-    # every gradient read twice; p, g, momentum read and written: 5 streams per element, 6 with the two global copies
-    nb = g16.numel() * 2.0 + g32.numel() * 4.0 + (p16.numel() * 2.0 + p32.numel() * 4.0) * (5.0 + len(glob) / 2)
+    # every gradient read twice; p, g, momentum read and written: 5 streams per element, 6 with the two global copies,
+    # and the fp32 lam of the dynamic step
+    nb = (g16.numel() * 2.0 + g32.numel() * 4.0 + (p16.numel() * 2.0 + p32.numel() * 4.0) * 5.0
+          + sum(float(t.numel() * t.element_size()) for t in glob))
     ev = _hbm(name, nb)
     call("mf_" + name, _p(p16), _p(g16), _p(b16), p16.numel(), _p(p32), _p(g32), _p(b32), p32.numel(), _p(chunks),
          nchunks, float(max_norm), _p(part), _p(out), _p(hyper), _p(halt_src), _p(input_flag), *map(_p, glob), _s())
@@ -735,6 +739,63 @@ def optimizer_step_prox(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm,
     _check_prox_hyper(hyper)
     _optimizer_call("optimizer_step_prox", p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper,
                     halt_src, input_flag, glob16, glob32)
+
+
+def _check_dyn_hyper(hyper):
+    if hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.numel() < 6:
+        raise ValueError("hyper: contiguous fp32 {lr, momentum, weight_decay, first_step, halt, alpha} (6 floats) "
+                         f"required, got {hyper.dtype} {tuple(hyper.shape)}")
+
+
+def _check_same_device(ref, named):
+    for name, t in named:
+        if t.device != ref.device:
+            raise ValueError(f"{name}: on {t.device}, the parameters are on {ref.device}")
+
+
+def sgd_dyn_step(p, g, buf, pglob, lam, coef, hyper):
+    """sgd_prox_step with FedDyn's linear term (mf_sgd_dyn_step): alpha * (p - pglob) - lam joins the clipped gradient.
+    hyper: device fp32 tensor {lr, momentum, weight_decay, first_step, halt, alpha}; pglob: the last global weights,
+    p's dtype and size; lam: the client's correction, fp32 of p's size whatever p's dtype; both buffers of their own."""
+    if p.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"p: fp16 or fp32 required, got {p.dtype}")
+    _check_flat("p", p, p.dtype)
+    for name, t in (("g", g), ("buf", buf), ("pglob", pglob)):
+        _check_flat(name, t, p.dtype, p.numel())
+    _check_flat("lam", lam, torch.float32, p.numel())
+    _check_same_device(p, (("g", g), ("buf", buf), ("pglob", pglob), ("lam", lam)))
+    if p.numel() and pglob.data_ptr() == p.data_ptr():
+        raise ValueError("pglob: a buffer of its own required (it is p)")
+    for oname, o in (("p", p), ("g", g), ("buf", buf), ("pglob", pglob)):
+        if _overlap(lam, o):
+            raise ValueError(f"lam: a buffer of its own required (it overlaps {oname})")
+    _check_dyn_hyper(hyper)
+    _sgd_call("sgd_dyn_step", p, g, buf, coef, hyper, pglob, lam)
+
+
+def optimizer_step_dyn(p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper, halt_src,
+                       input_flag=None, glob16=None, glob32=None, lam=None):
+    """optimizer_step_prox with the dynamic SGD launch (mf_optimizer_step_dyn): hyper has 6 floats (alpha at [5]) and
+    lam is fp32 of n16 + n32 elements in the bucket's order [fp16 trainables | fp32 trainables]."""
+    if glob16 is None or glob32 is None or lam is None:
+        raise ValueError("optimizer_step_dyn: glob16, glob32 (the global copies) and lam are required")
+    _check_flat("p16", p16, torch.float16)
+    _check_flat("p32", p32, torch.float32)
+    for name, t, ref in (("g16", g16, p16), ("b16", b16, p16), ("glob16", glob16, p16), ("g32", g32, p32),
+                         ("b32", b32, p32), ("glob32", glob32, p32)):
+        _check_flat(name, t, ref.dtype, ref.numel())
+    _check_flat("lam", lam, torch.float32, p16.numel() + p32.numel())
+    named = (("p32", p32), ("g16", g16), ("b16", b16), ("g32", g32), ("b32", b32), ("glob16", glob16),
+             ("glob32", glob32))
+    _check_same_device(p16, named + (("lam", lam),))
+    if (p16.numel() and glob16.data_ptr() == p16.data_ptr()) or (p32.numel() and glob32.data_ptr() == p32.data_ptr()):
+        raise ValueError("glob16 / glob32: buffers of their own required")
+    for oname, o in (("p16", p16),) + named:
+        if _overlap(lam, o):
+            raise ValueError(f"lam: a buffer of its own required (it overlaps {oname})")
+    _check_dyn_hyper(hyper)
+    _optimizer_call("optimizer_step_dyn", p16, g16, b16, p32, g32, b32, chunks, nchunks, max_norm, part, out, hyper,
+                    halt_src, input_flag, glob16, glob32, lam)
 
 
 def fedavg_pack_weighted(p16, p32, invalid_flag, weight, bucket):
@@ -840,6 +901,55 @@ def fedopt_deliver(x, p16, p32, g16, g32):
         if _overlap(x, o):
             raise ValueError(f"x: a buffer of its own required (it overlaps {oname})")
     call("mf_fedopt_deliver", _p(x), _p(p16), p16.numel(), _p(p32), p32.numel(), _p(g16), _p(g32), _s())
+
+
+def _check_feddyn(bucket, alpha, h, lam, flag, p16, p32, g16, g32):
+    import math
+    alpha = float(alpha)
+    if not math.isfinite(alpha) or alpha <= 0.0:
+        raise ValueError(f"alpha: finite and > 0 required, got {alpha}")
+    _check_fedopt_outputs(p16, p32, g16, g32)
+    n = p16.numel() + p32.numel()
+    if bucket.dtype != torch.float32 or not bucket.is_contiguous() or bucket.numel() < n + 1:
+        raise ValueError("bucket: contiguous fp32 of at least n16 + n32 + 1 floats (the plain layout) required")
+    if h is None or lam is None:
+        raise ValueError("h, lam: the FedDyn state is required")
+    _check_flat("h", h, torch.float32, n)
+    _check_flat("lam", lam, torch.float32, n)
+    if flag is None or flag.dtype != torch.int32 or flag.numel() < 1:
+        raise ValueError("flag: the client's int32 device flag is required")
+    _check_same_device(p16, (("p32", p32), ("g16", g16), ("g32", g32), ("bucket", bucket), ("h", h), ("lam", lam),
+                             ("flag", flag)))
+    others = [("bucket", bucket[:n + 1]), ("p16", p16), ("p32", p32), ("g16", g16), ("g32", g32)]
+    for name, t, rest in (("h", h, [("lam", lam)] + others), ("lam", lam, others)):
+        for oname, o in rest:
+            if _overlap(t, o):
+                raise ValueError(f"{name}: a buffer of its own required (it overlaps {oname})")
+    return alpha, n
+
+
+def feddyn_step(bucket, alpha, num_clients, h, lam, flag, p16, p32, g16, g32):
+    """FedDyn's round end on the summed plain bucket (mf_feddyn_step): h, the server's mean of the num_clients
+    corrections, steps; this client's lam updates unless its flag is set; fp16(mean - h / alpha) goes into its weights
+    and global copy.  h, lam: fp32 of n16 + n32 elements, buffers of their own."""
+    if isinstance(num_clients, bool) or int(num_clients) != num_clients or num_clients < 1:
+        raise ValueError(f"num_clients: an integer >= 1 required, got {num_clients!r}")
+    alpha, n = _check_feddyn(bucket, alpha, h, lam, flag, p16, p32, g16, g32)
+    # bucket read; h, lam read and written; the weights and the global copy read and written
+    ev = _hbm("feddyn_step", n * 20.0 + p16.numel() * 8.0 + p32.numel() * 16.0)
+    call("mf_feddyn_step", _p(bucket), alpha, int(num_clients), _p(h), _p(lam), _p(flag), _p(p16), p16.numel(),
+         _p(p32), p32.numel(), _p(g16), _p(g32), _s())
+    _rec(ev)
+
+
+def feddyn_deliver(bucket, alpha, h, lam, flag, p16, p32, g16, g32):
+    """The rank's second and later clients after feddyn_step (mf_feddyn_deliver): the stepped h is only read, the same
+    fp16(mean - h / alpha) delivered, this client's own lam updated."""
+    alpha, n = _check_feddyn(bucket, alpha, h, lam, flag, p16, p32, g16, g32)
+    ev = _hbm("feddyn_deliver", n * 16.0 + p16.numel() * 8.0 + p32.numel() * 16.0)
+    call("mf_feddyn_deliver", _p(bucket), alpha, _p(h), _p(lam), _p(flag), _p(p16), p16.numel(), _p(p32), p32.numel(),
+         _p(g16), _p(g32), _s())
+    _rec(ev)
 
 
 def fedavg_reduce_ordered(gathered, nclients, out):

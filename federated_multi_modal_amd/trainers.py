@@ -34,8 +34,8 @@ import torch.distributed as dist
 from . import ops
 from .data import DATASET_CLASSES, SyntheticClientDataManager, unified_classnames
 from .engine import EngineConfig, MapleEngine
-from .federated import (ROBUST, SERVER_OPTS, FedAvgBucket, FedAvgExchange, FederatedAbort, ServerOptimizer,
-                        dp_epsilon, resolve_client_weights)
+from .federated import (ROBUST, SERVER_OPTS, FedAvgBucket, FedAvgExchange, FedDynState, FederatedAbort,
+                        ServerOptimizer, dp_epsilon, resolve_client_weights)
 from .captions import caption_tokens, draw_caption_weights, has_captions
 from .modules import CustomCLIP
 from .schedule import HostLR
@@ -723,6 +723,32 @@ class MaPLeFederated(TrainerX):
                                  "longer has an L2 norm within the bound)")
         return {"compress": None if name == "none" else name, "rounding": rounding, "error_feedback": ef, "seed": seed}
 
+    def _dyn_cfg(self, get, mu, server_opt, robust):
+        """FED.DYN_ALPHA, validated: alpha, 0.0 = off.  ValueError for a value that is no number, non-finite or < 0,
+        and for alpha > 0 together with an option under which h is no longer the mean of the clients' corrections."""
+        alpha = get("DYN_ALPHA", 0.0)
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)):
+            raise ValueError(f"FED.DYN_ALPHA {alpha!r}: a number")
+        alpha = float(alpha)
+        if not math.isfinite(alpha) or alpha < 0.0:
+            raise ValueError(f"FED.DYN_ALPHA {alpha}: FedDyn's alpha is finite and >= 0 (0 = off)")
+        if alpha == 0.0:
+            return 0.0
+        if mu > 0.0:
+            raise ValueError(f"FED.PROX_MU {mu:g}: not with FED.DYN_ALPHA {alpha:g} (the dynamic step already holds the "
+                             "proximal term, with alpha in mu's place)")
+        why = ("FedDyn's h is the mean of the clients' corrections only while the server sees the clients' own weights "
+               "in a plain mean")
+        spec = get("CLIENT_WEIGHTS", "uniform")
+        for key, value, on in (("SERVER_OPT", server_opt, server_opt != "none"),
+                               ("CLIENT_WEIGHTS", spec, self.client_weights is not None),
+                               ("ROBUST_AGG", robust, robust is not None),
+                               ("DP_CLIP", self.dp["clip"], self.dp["clip"] is not None),
+                               ("COMPRESS", self.compress["compress"], self.compress["compress"] is not None)):
+            if on:
+                raise ValueError(f"FED.{key} {value!r}: not with FED.DYN_ALPHA {alpha:g} ({why})")
+        return alpha
+
     def _compress_report(self):
         """Rank 0's line under FED.COMPRESS, once: the uplink bytes per client and round with and without compression."""
         cp = getattr(self, "compress", None)
@@ -764,7 +790,8 @@ class MaPLeFederated(TrainerX):
         FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
         FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
         (coordinate-wise median / trimmed mean, Yin et al.), FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
-        McMahan et al. 2018) and FED.COMPRESS (int8 uplink compression with error feedback, Alistarh et al.)."""
+        McMahan et al. 2018), FED.COMPRESS (int8 uplink compression with error feedback, Alistarh et al.) and
+        FED.DYN_ALPHA (FedDyn, Acar et al.)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
@@ -781,6 +808,7 @@ class MaPLeFederated(TrainerX):
             total = sum(self.client_weights)
             print("[INFO] FedAvg client weights: " + ", ".join(
                 f"client {i}: {w:g} ({100.0 * w / total:.1f} %)" for i, w in enumerate(self.client_weights)))
+        alpha = self._dyn_cfg(get, mu, server_opt, robust)
         self.clients = []
         for i in self._local_client_ids():
             self.clients.append(MaPLe(self.cfg, client_id=i, classnames=global_classnames,
@@ -793,10 +821,13 @@ class MaPLeFederated(TrainerX):
         self.server = None if server_opt == "none" else ServerOptimizer(
             server_opt, c0.engine, lr=server_hp["FED.SERVER_LR"], beta1=server_hp["FED.SERVER_MOMENTUM"],
             beta2=server_hp["FED.SERVER_BETA2"], tau=server_hp["FED.SERVER_TAU"])
+        # ... and one FedDyn state (h, the mean of all the clients' corrections)
+        self.dyn = None if alpha == 0.0 else FedDynState(alpha, c0.engine, self.num_clients)
         self.fed = [FedAvgBucket(c.engine, mode=mode, weight=None if cw is None else cw[c.client_id],
                                  server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"],
                                  compress=cp["compress"], compress_rounding=cp["rounding"],
-                                 error_feedback=cp["error_feedback"], compress_seed=cp["seed"], client=c.client_id)
+                                 error_feedback=cp["error_feedback"], compress_seed=cp["seed"], client=c.client_id,
+                                 dyn=self.dyn)
                     for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k, dp_std=self.dp["std"],
                                        dp_seed=self.dp["seed"])
@@ -807,6 +838,12 @@ class MaPLeFederated(TrainerX):
             print(f"[INFO] FedProx: mu = {mu:g}")
             for c, fed in zip(self.clients, self.fed):
                 c.engine.set_proximal(mu, fed.global16, fed.global32)
+        if self.dyn is not None:
+            # FedDyn: every local step reads the bucket's global copy and its client's correction, both updated in
+            # place by each unpack, so the pointers go in before a client captures its training step
+            print(f"[INFO] FedDyn: alpha = {alpha:g}")
+            for c, fed in zip(self.clients, self.fed):
+                c.engine.set_dynamic(alpha, fed.global16, fed.global32, fed.lam)
         self.global_weights = self.clients[0].model.state_dict()
 
     # ---------------------------------------------------------------- round loop
@@ -1050,6 +1087,9 @@ class MaPLeFederated(TrainerX):
                 for fed in self.fed:
                     fed.load_state_dict({"residual": None})
                 print("The uplink compression's error-feedback residuals restart at zero.")
+            # neither are FedDyn's corrections (one fp32 bucket per client, and h): snapshot() above zeroed them
+            if getattr(self, "dyn", None) is not None:
+                print("FedDyn's corrections (every client's lambda and the server's h) restart at zero.")
             # ... and the server optimizer starts from them, unless the checkpoint carries its state
             server = getattr(self, "server", None)
             if server is not None and ckpt.get("server_optimizer") is not None:

@@ -272,6 +272,27 @@ int mf_optimizer_step_prox(void* p16, void* g16, void* b16, int64_t n16, float* 
                            int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
                            float* hyper, const float* halt_src, const int* input_flag, const void* glob16,
                            const float* glob32, void* stream);
+/* FedDyn local step (Acar, Zhao, Matas Navarro, Mattina, Whatmough, Saligrama: "Federated Learning Based on Dynamic
+ * Regularization", ICLR 2021): the local objective gains -<lam, w> + (alpha/2) ||w - w_global||^2.  hyper (device):
+ * {lr, momentum, weight_decay, first_step, halt, alpha}, alpha in the slot mf_sgd_prox_step reads mu from.  lam: the
+ * client's linear correction, n fp32 elements whatever the buffer's dtype T (it accumulates alpha * (w - w_global)
+ * over the rounds, increments an fp16 accumulator would round away), read only.  Per element, every line rounded to T,
+ * the scalars fp32, no fused multiply-add:
+ *   g = gc = T(g * coef);  d = T(p - pglob);  gp = T(gc + alpha * d);  gl = T(gp - lam)   (one fp32 subtraction,
+ *   then the rounding to T);  d_p = T(gl + wd * p);  momentum and parameter update as mf_sgd_step.
+ * lam == 0 gives mf_sgd_prox_step's result at mu = alpha bit for bit.  halt != 0 leaves p, g and buf untouched.
+ * pglob and lam must not overlap p, g or buf.                                                                */
+int mf_sgd_dyn_step(void* p, void* g, void* buf, const void* pglob, const float* lam, int64_t n, int is16,
+                    const float* coef, const float* hyper, void* stream);
+/* mf_optimizer_step_prox with the dynamic SGD launch (three launches): its arguments plus lam, n16 + n32 fp32
+ * elements in the bucket's order [fp16 trainables | fp32 trainables]: the fp16 buffer's step reads lam[0:n16], the fp32
+ * buffer's lam[n16:].  Bit-identical to mf_clip_grad_norm + the halt latch + mf_sgd_dyn_step(fp16, lam) +
+ * mf_sgd_dyn_step(fp32, lam + n16); 8 elements per thread under mf_optimizer_step_prox's rule with lam 32-byte
+ * aligned (lam + n16 then is exactly when n16 % 8 == 0).                                                      */
+int mf_optimizer_step_dyn(void* p16, void* g16, void* b16, int64_t n16, float* p32, float* g32, float* b32,
+                          int64_t n32, const void* chunks, int nchunks, float max_norm, float* part, float* out,
+                          float* hyper, const float* halt_src, const int* input_flag, const void* glob16,
+                          const float* glob32, const float* lam, void* stream);
 /* Sample-weighted FedAvg (McMahan, Moore, Ramage, Hampson, Aguera y Arcas: "Communication-Efficient Learning of
  * Deep Networks from Decentralized Data", AISTATS 2017): w_global = sum_k n_k w_k / sum_k n_k.  The weight travels
  * in the bucket, n = n16 + n32: pack writes n + 2 floats, bucket[0:n] = fp32(weight) * float(p) (0 if
@@ -325,6 +346,28 @@ int mf_fedopt_step(const float* bucket, int weighted, int opt, float beta1, floa
  * second and later clients of a rank after mf_fedopt_step wrote the first.  Changes no state.                    */
 int mf_fedopt_deliver(const float* x, void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32,
                       void* stream);
+/* FedDyn's round end (Acar et al., ICLR 2021, Algorithm 1), one launch per local client in mf_fedavg_unpack's place
+ * on the summed plain bucket [sum over the valid clients | votes], n = n16 + n32.  h: the server's state, the mean of
+ * the N = num_clients clients' lam, n fp32 elements in the bucket's order; lam: this client's correction, the same
+ * shape; flag: the client's device flag (non-zero: invalid or failed, it did not take part).  Per element i, with
+ * w = float(p_i) the client's local weight and q = float(g_i) the round's starting weight (its global copy), both
+ * read before anything is written, every binary operation one IEEE fp32 operation, no fused multiply-add;
+ * frac = votes / (float)N and af = alpha * frac are formed once in the kernel:
+ *   votes == 0:   p = g;  h and lam untouched
+ *   client:       if *flag == 0:  lam = lam - alpha * (w - q)
+ *   server:       mean = sum / votes;  h = h - af * (mean - q)             (mf_feddyn_step only)
+ *   both:         mean = sum / votes;  x = mean - h / alpha  (the stepped h);
+ *                 val = fp16(x);  p16 = g16 = val;  p32 = g32 = float(val)
+ * An absent client keeps its lam (the paper's rule for a device that did not take part) and reaches h through frac.
+ * mf_feddyn_deliver serves the rank's second and later clients: it reads the stepped h and the same bucket, so it
+ * recomputes the same x (no fp32 copy of x is kept), and updates that client's own lam from its own p and g.
+ * 8 elements per thread when n16 % 8 == n32 % 8 == 0 and bucket, h, lam, p32, g32 are 32-byte aligned (p16 / g16:
+ * 16), one per thread otherwise; the same bits either way.  h, lam, the bucket and the weight buffers must not
+ * overlap.  Errors: negative sizes, alpha not finite and > 0, num_clients < 1, a null pointer.                     */
+int mf_feddyn_step(const float* bucket, float alpha, int num_clients, float* h, float* lam, const int* flag,
+                   void* p16, int64_t n16, float* p32, int64_t n32, void* g16, float* g32, void* stream);
+int mf_feddyn_deliver(const float* bucket, float alpha, const float* h, float* lam, const int* flag, void* p16,
+                      int64_t n16, float* p32, int64_t n32, void* g16, float* g32, void* stream);
 /* FedAvg in client order (trainers/maple_fed.py:311-314: torch.stack over the clients, then mean):   */
 /* out[i] = sum_c gathered[c * stride + i] accumulated c = 0, 1, ... in fp32, for i < n; gathered    */
 /* holds every client's packed bucket (an all-gather of mf_fedavg_pack outputs)                      */
