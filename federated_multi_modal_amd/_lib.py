@@ -81,6 +81,9 @@ SIGNATURES = {
     "mf_compress_quantize": [P, P, L, P, P, L, P, P, P, F, I, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, P, L, L,
                              I, P],
     "mf_compress_decode": [P, L, I, L, L, L, P, L, P, L, I, P, L, P],
+    "mf_topk_chunk_bytes": [L, I],
+    "mf_topk_select": [P, P, L, P, P, L, P, P, P, F, I, P, L, L, I, P],
+    "mf_topk_decode": [P, L, I, L, L, L, P, L, P, L, I, P, L, I, P],
     "mf_seq_grow": [P, P, P, P, I, I, I, I, I, P],
     "mf_seq_grow_bwd": [P, P, I, I, I, I, I, P],
     "mf_seq_scatter": [P, L, P, L, I, I, I, I, P],
@@ -94,10 +97,10 @@ SIGNATURES = {
 _VALUE_FUNCS = {"mf_abi_version", "mf_layernorm_bwd_blocks", "mf_colsum_blocks", "mf_optim_chunk_bytes",
                 "mf_optim_chunk_elems", "mf_col_reduce_desc_bytes", "mf_small_linear_desc_bytes",
                 "mf_gemm_splitk_ws_floats", "mf_augment_ws_bytes", "mf_qkv_attention_supported", "mf_dp_update_ws_floats",
-                "mf_compress_chunk_bytes"}
+                "mf_compress_chunk_bytes", "mf_topk_chunk_bytes"}
 # value functions whose return type is not int
 _RESTYPES = {"mf_augment_ws_bytes": ctypes.c_int64, "mf_dp_update_ws_floats": ctypes.c_int64,
-             "mf_compress_chunk_bytes": ctypes.c_int64}
+             "mf_compress_chunk_bytes": ctypes.c_int64, "mf_topk_chunk_bytes": ctypes.c_int64}
 
 _LIB = None
 

@@ -244,12 +244,18 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # seed of the noise stream; -1 = max(SEED, 0).  It comes from this file: a reproducible
                            # simulation of the mechanism, not a hardened deployment
                            DP_SEED=-1,
-                           # int8 compression of the FedAvg uplink (QSGD, Alistarh et al., NeurIPS 2017): "none" or
-                           # "int8" -- each client's update w_k - w_global travels as 8-bit codes with one fp32 scale
+                           # compression of the FedAvg uplink: "none", "int8" or "topk".  "int8" (QSGD, Alistarh et al.,
+                           # NeurIPS 2017): each client's update w_k - w_global travels as 8-bit codes with one fp32 scale
                            # per 256 coordinates, 1 + 1/64 bytes per coordinate instead of 4.  The sharded "ordered"
                            # exchange over several ranks moves fewer bytes; "allreduce" and one process only simulate
-                           # the arithmetic.  Not with DP_CLIP
+                           # the arithmetic.  Not with DP_CLIP.  "topk": from every block of 256 coordinates only the
+                           # COMPRESS_TOPK of largest magnitude travel, as (uint8 index, fp32 value); the others stay in
+                           # the residual (Aji & Heafield 2017; Stich et al., NeurIPS 2018).  Not with ROBUST_AGG or
+                           # stochastic rounding
                            COMPRESS="none",
+                           # entries kept per block of 256 under COMPRESS "topk": 1 to 64 (8: 40 bytes per block, 1024 in
+                           # fp32)
+                           COMPRESS_TOPK=8,
                            # "nearest", or "stochastic" (unbiased; its bits follow COMPRESS_SEED, the round and the client)
                            COMPRESS_ROUNDING="nearest",
                            # keep each client's rounding error and add it to its next update (Seide et al. 2014;

@@ -117,6 +117,18 @@ round, reproduces the same codes, and the residual is applied once; an invalid o
 scales and vote 0) and keeps its residual.  Not combined with dp_clip / dp_std: a quantised, fed-back update no longer
 has an L2 norm within the bound.
 
+Top-k sparsification of the uplink with error feedback (FedAvgBucket compress="topk", compress_k=8; FED.COMPRESS topk,
+FED.COMPRESS_TOPK): the same update u, the same residual and its two-buffer commit, the same send image and the same
+places for the decode, but from every block of 256 coordinates only the k of largest magnitude travel, as (uint8 index
+within the block, fp32 value), a tie going to the lower index (Aji & Heafield, EMNLP 2017; Stich et al., NeurIPS 2018;
+Lin et al., ICLR 2018; Sattler et al. 2019): chunk = 4 nb k + 4 ceil(nb k / 4) + 8 bytes for a shard of nb blocks, 40
+bytes per block at k = 8 where the fp32 bucket moves 1024 and int8 moves 260.  Nothing is rounded: a coordinate's update
+is sent whole (e' = 0) or stays whole in the residual (e' = u), and the receiver adds the sent value, or +0, to the
+global copy (mf_topk_select, mf_topk_decode).  The blocks start at coordinate 0 whatever the world size, so every layout
+gives the same bits.  Not with stochastic rounding (there is nothing to round), not with the robust aggregation (most
+coordinates of every client decode to g itself, so a median returns g unless half the clients kept the coordinate), and,
+as int8, not with dp_clip / dp_std or dyn.
+
 FedDyn (FedAvgBucket dyn= / FedDynState; FED.DYN_ALPHA, off by default): the dynamic regularisation of Acar, Zhao, Matas
 Navarro, Mattina, Whatmough and Saligrama (ICLR 2021), which makes the clients' local optima agree with the global one
 where FedProx only pulls them towards the last global model.  Client k minimises L_k(w) - <lam_k, w> + (alpha / 2)
@@ -147,7 +159,8 @@ from . import ops
 MODES = ("ordered", "allreduce")
 ROBUST = ("median", "trimmed_mean")
 MEDIAN_TRIM = ops.MEDIAN_TRIM  # a trim no client count reaches: the trimmed reduce degrades it to the median
-COMPRESS = ("int8",)
+COMPRESS = ("int8", "topk")
+TOPK_MAX = ops.TOPK_MAX  # entries kept per block of COMPRESS_BLOCK coordinates, at most
 COMPRESS_ROUNDINGS = tuple(ops.COMPRESS_ROUNDINGS)
 COMPRESS_BLOCK = ops.COMPRESS_BLOCK  # coordinates per quantisation block; a compressed shard is a multiple of it
 
@@ -214,6 +227,9 @@ class _HipKernels:
     compress_chunk_bytes = staticmethod(ops.compress_chunk_bytes)
     compress_quantize = staticmethod(ops.compress_quantize)
     compress_decode = staticmethod(ops.compress_decode)
+    topk_chunk_bytes = staticmethod(ops.topk_chunk_bytes)
+    topk_select = staticmethod(ops.topk_select)
+    topk_decode = staticmethod(ops.topk_decode)
     feddyn_step = staticmethod(ops.feddyn_step)
     feddyn_deliver = staticmethod(ops.feddyn_deliver)
 
@@ -380,9 +396,10 @@ class FedAvgBucket:
     whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8") sends the update as int8 codes
     with block scales instead (module docstring): `compress_rounding` "nearest" | "stochastic", `error_feedback` keeps
     the rounding error as a per-client residual (state_dict() / load_state_dict() carry it), `compress_seed` and
-    `client`, the global client index, select the stochastic rounding's bits.  `dyn` (the process's FedDynState) selects
-    FedDyn (module docstring): the bucket keeps its client's correction `lam` and unpack() runs the round's end; not with
-    weight, robust, dp_clip, compress or server.
+    `client`, the global client index, select the stochastic rounding's bits; `compress` "topk" sends the `compress_k`
+    (1..64) entries of largest magnitude of every block of 256 coordinates instead, with the same residual.  `dyn` (the
+    process's FedDynState) selects FedDyn (module docstring): the bucket keeps its client's correction `lam` and unpack()
+    runs the round's end; not with weight, robust, dp_clip, compress or server.
 
     pack() / unpack() are the per-client halves; start() / finish() / run() exchange this one bucket
     alone (one client per rank: the bench and the single-client tests).  Several clients per rank
@@ -393,7 +410,7 @@ class FedAvgBucket:
                  server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1,
                  dp_clip: Optional[float] = None, compress: Optional[str] = None, compress_rounding: str = "nearest",
                  error_feedback: bool = True, compress_seed: int = 0, client: int = 0,
-                 dyn: Optional["FedDynState"] = None):
+                 dyn: Optional["FedDynState"] = None, compress_k: int = 8):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         if compress is not None and compress not in COMPRESS:
@@ -404,9 +421,18 @@ class FedAvgBucket:
             raise ValueError(f"FedAvg compress_seed {compress_seed!r}: an integer in [0, 2**64)")
         if isinstance(client, bool) or not isinstance(client, int) or not 0 <= client < 2 ** 31:
             raise ValueError(f"FedAvg client {client!r}: the global client index, an integer in [0, 2**31)")
+        if isinstance(compress_k, bool) or not isinstance(compress_k, int) or not 1 <= compress_k <= TOPK_MAX:
+            raise ValueError(f"FedAvg compress_k {compress_k!r}: an integer from 1 to {TOPK_MAX}")
         if compress is not None and dp_clip is not None:
             raise ValueError("FedAvg compress with dp_clip: a quantised, fed-back update no longer has an L2 norm "
                              "within the bound")
+        if compress == "topk" and compress_rounding == "stochastic":
+            raise ValueError('FedAvg compress "topk" with compress_rounding "stochastic": the kept values travel as '
+                             "fp32, there is nothing to round")
+        if compress == "topk" and robust is not None:
+            raise ValueError('FedAvg compress "topk" with robust aggregation: most coordinates of every client decode '
+                             "to the global copy itself, so a coordinate-wise median returns it unless half the "
+                             "clients kept that coordinate")
         if dyn is not None:
             for label, on in (("a client weight", weight is not None), ("robust aggregation", robust is not None),
                               ("dp_clip", dp_clip is not None), ("compress", compress is not None),
@@ -417,7 +443,7 @@ class FedAvgBucket:
             if (dyn.n16, dyn.n32) != (engine.n16, engine.n32):
                 raise ValueError("FedAvgBucket: the FedDyn state was built for other sizes")
         self.compress, self.compress_rounding, self.error_feedback = compress, compress_rounding, bool(error_feedback)
-        self.compress_seed, self.client = compress_seed, client
+        self.compress_seed, self.client, self.compress_k = compress_seed, client, compress_k
         if dp_clip is not None:
             dp_clip = float(dp_clip)
             if not math.isfinite(dp_clip) or dp_clip <= 0.0:
@@ -502,9 +528,13 @@ class FedAvgBucket:
             if self._wire is None:
                 self.exchange  # this bucket alone: its exchange owns the image
             x, slot = self._wire
-            self.k.compress_quantize(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
-                                     self.flag, self.weight, self.compress_rounding, self.compress_seed, x.round,
-                                     self.client, x.image, slot, x.S)
+            if self.compress == "topk":  # ... or as the k largest entries of every block, (index, fp32 value)
+                self.k.topk_select(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
+                                   self.flag, self.weight, self.compress_k, x.image, slot, x.S)
+            else:
+                self.k.compress_quantize(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
+                                         self.flag, self.weight, self.compress_rounding, self.compress_seed, x.round,
+                                         self.client, x.image, slot, x.S)
             self._resid_due = self.resid is not None and not failed
         elif self.dp_clip is not None and not failed:
             # the update against the weights the round started from, its clip scale left on the device for the pack
@@ -667,8 +697,8 @@ class FedAvgExchange:
         if isinstance(dp_seed, bool) or not isinstance(dp_seed, int) or not 0 <= dp_seed < 2 ** 64:
             raise ValueError(f"FedAvg dp_seed {dp_seed!r}: an integer in [0, 2**64)")
         self.b = list(buckets)
-        if len({None if x.compress is None else (x.compress, x.compress_rounding, x.error_feedback, x.compress_seed)
-                for x in self.b}) > 1:
+        if len({None if x.compress is None else (x.compress, x.compress_rounding, x.error_feedback, x.compress_seed,
+                                                 x.compress_k) for x in self.b}) > 1:
             raise ValueError("FedAvg compress: the buckets of one exchange differ in their compression settings")
         assert self.b and len({x.pbuf.numel() for x in self.b}) == 1
         # one layout per exchange: every bucket weighted (n + 2 floats) or none (n + 1)
@@ -703,13 +733,15 @@ class FedAvgExchange:
         # int8 compression of the uplink: one setting per exchange; the uint8 send image [dest rank][client][chunk] the
         # buckets' packs write into, and under the sharded chain the image the all_to_all fills
         self.compress = b0.compress
-        self.image = self.recv_image = None
+        self.image = self.recv_image = self.topk = None
         if self.compress is not None:
             if b0.compress_rounding == "stochastic" and len({x.client for x in self.b}) != self.C:
                 raise ValueError("FedAvg compress: two buckets of one exchange carry the same client index (their "
                                  "rounding bits would coincide)")
             self.layout = "robust" if b0.robust is not None else ("plain" if b0.weight is None else "weighted")
-            self.chunk = self.k.compress_chunk_bytes(self.S)
+            self.topk = b0.compress_k if self.compress == "topk" else None
+            self.chunk = (self.k.compress_chunk_bytes(self.S) if self.topk is None
+                          else self.k.topk_chunk_bytes(self.S, self.topk))
             self.image = torch.zeros(self.world, self.C, self.chunk, device=dev, dtype=torch.uint8)
             if self.sharded:
                 self.recv_image = torch.empty(self.world * self.C * self.chunk, device=dev, dtype=torch.uint8)
@@ -751,8 +783,12 @@ class FedAvgExchange:
         is saved here: the compression is simulated."""
         img = self.image.view(-1)
         for j, x in enumerate(self.b):
-            self.k.compress_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
-                                   x.global16, x.global32, self.layout, x.pbuf, self.S)
+            if self.topk is not None:
+                self.k.topk_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
+                                   x.global16, x.global32, self.layout, x.pbuf, self.S, self.topk)
+            else:
+                self.k.compress_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
+                                       x.global16, x.global32, self.layout, x.pbuf, self.S)
 
     def _local_sum(self) -> torch.Tensor:
         """The rank's buckets summed in client order (== torch.stack(...) order over these clients)."""
@@ -817,9 +853,14 @@ class FedAvgExchange:
             if hs:
                 self.recv_image.copy_(rimg)
             b0 = self.b[0]
-            self.k.compress_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
+            if self.topk is not None:
+                self.k.topk_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
                                    dist.get_rank(self.group) * self.S, 0, b0.global16, b0.global32, self.layout,
-                                   self.recv, self.S)
+                                   self.recv, self.S, self.topk)
+            else:
+                self.k.compress_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
+                                       dist.get_rank(self.group) * self.S, 0, b0.global16, b0.global32, self.layout,
+                                       self.recv, self.S)
         if self.trim is None:
             self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
         else:  # the robust statistic of this rank's shard; the vote element, if it lies in this shard, counts

@@ -1170,5 +1170,97 @@ def compress_decode(image, nclients, chunk_stride, S, first, first_step, g16, g3
     _rec(ev)
 
 
+TOPK_MAX = 64  # entries kept per block of COMPRESS_BLOCK coordinates, at most: one lane each
+TOPK_LAYOUTS = ("plain", "weighted")
+
+
+def _check_topk(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"k: an integer from 1 to {TOPK_MAX} required, got {k!r}")
+    return k
+
+
+def topk_chunk_bytes(S: int, k: int) -> int:
+    """Bytes of one top-k wire chunk of shard length S: [S / 256 * k fp32 values | S / 256 * k uint8 indices | zero
+    bytes to a multiple of 4 | fp32 weight | fp32 vote] (mf_topk_chunk_bytes)."""
+    S, k = int(S), _check_topk(k)
+    if S <= 0 or S % COMPRESS_BLOCK:
+        raise ValueError(f"S: a positive multiple of {COMPRESS_BLOCK} required, got {S}")
+    return int(call("mf_topk_chunk_bytes", S, k))
+
+
+def topk_select(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, k, image, slot, S):
+    """The k entries of largest magnitude of every block of 256 coordinates of the update [p16 | p32] - [g16 | g32]
+    (+ e_in, the residual; e_out receives the new one, zero where a coordinate was sent; both None: no error feedback),
+    as (uint8 index, fp32 value), and the tail, written into image[:, slot, :], the exchange's uint8 send image
+    [destination rank][local client][topk_chunk_bytes(S, k)] (mf_topk_select, include/mapfed.h).  weight: the tail's
+    weight (None: 1)."""
+    import math
+    weight = 1.0 if weight is None else float(weight)
+    if not math.isfinite(weight) or weight <= 0.0:
+        raise ValueError(f"weight: finite and > 0 required, got {weight}")
+    slot, S = int(slot), int(S)
+    _check_dp_pairs(p16, g16, p32, g32)
+    n = p16.numel() + p32.numel()
+    chunk = topk_chunk_bytes(S, k)
+    if image.dtype != torch.uint8 or image.dim() != 3 or not image.is_contiguous() or image.shape[2] != chunk:
+        raise ValueError(f"image: contiguous uint8 [ranks][clients][{chunk}] required, got {image.dtype} "
+                         f"{tuple(image.shape)}")
+    world, C = image.shape[0], image.shape[1]
+    if not 0 <= slot < C:
+        raise ValueError(f"slot: 0 to {C - 1} required, got {slot}")
+    if world * S < n:
+        raise ValueError(f"image: {world} shards of {S} hold fewer than the {n} coordinates")
+    if (e_in is None) != (e_out is None):
+        raise ValueError("e_in / e_out: both residual buffers or neither")
+    if e_in is not None:
+        _check_flat("e_in", e_in, torch.float32, n)
+        _check_flat("e_out", e_out, torch.float32, n)
+        if _overlap(e_in, e_out):
+            raise ValueError("e_out: a buffer of its own required (it overlaps e_in)")
+    if invalid_flag is None or invalid_flag.dtype != torch.int32 or invalid_flag.numel() < 1:
+        raise ValueError("invalid_flag: an int32 tensor required")
+    for oname, o in (("p16", p16), ("g16", g16), ("p32", p32), ("g32", g32), ("e_in", e_in), ("e_out", e_out)):
+        if _overlap(image, o):
+            raise ValueError(f"image: a buffer of its own required (it overlaps {oname})")
+    # weights, global copy and residual read, the residual and the chunks written
+    ev = _hbm("topk_select", p16.numel() * 4.0 + p32.numel() * 8.0 + (8.0 * n if e_in is not None else 0.0)
+              + world * float(chunk))
+    call("mf_topk_select", _p(p16), _p(g16), p16.numel(), _p(p32), _p(g32), p32.numel(), _p(e_in), _p(e_out),
+         _p(invalid_flag), weight, k, image.data_ptr() + slot * chunk, C * chunk, S, world, _s())
+    _rec(ev)
+
+
+def topk_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride, k):
+    """nclients top-k wire chunks, image[c * chunk_stride:] (a flat uint8 tensor, bytes), decoded into
+    out[c * out_stride: c * out_stride + S] (fp32) as compress_decode does: g plus the sent value at a kept coordinate,
+    g + 0 elsewhere, in layout "plain" or "weighted" (mf_topk_decode, include/mapfed.h)."""
+    if layout not in TOPK_LAYOUTS:
+        raise ValueError(f"layout: one of {TOPK_LAYOUTS}, got {layout!r}")
+    nclients, chunk_stride, S, first, first_step, out_stride = (int(v) for v in (nclients, chunk_stride, S, first,
+                                                                                  first_step, out_stride))
+    chunk = topk_chunk_bytes(S, k)
+    if nclients < 1 or first < 0 or first_step < 0:
+        raise ValueError(f"nclients >= 1, first >= 0 and first_step >= 0 required, got {nclients}, {first}, {first_step}")
+    if chunk_stride % 4 or (nclients > 1 and (chunk_stride < chunk or out_stride < S)):
+        raise ValueError(f"chunk_stride: a multiple of 4 of at least {chunk} bytes, and out_stride at least {S}, "
+                         f"required, got {chunk_stride}, {out_stride}")
+    if image.dtype != torch.uint8 or not image.is_contiguous() or image.numel() < (nclients - 1) * chunk_stride + chunk:
+        raise ValueError(f"image: contiguous uint8 of at least {(nclients - 1) * chunk_stride + chunk} bytes required, "
+                         f"got {image.dtype} {tuple(image.shape)}")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < (nclients - 1) * out_stride + S:
+        raise ValueError(f"out: contiguous fp32 of at least {(nclients - 1) * out_stride + S} floats required, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    _check_flat("g16", g16, torch.float16)
+    _check_flat("g32", g32, torch.float32)
+    for oname, o in (("image", image), ("g16", g16), ("g32", g32)):
+        if _overlap(out, o):
+            raise ValueError(f"out: a buffer of its own required (it overlaps {oname})")
+    ev = _hbm("topk_decode", nclients * (float(chunk) + 4.0 * S + 3.0 * S))  # chunk and g read, the image written
+    call("mf_topk_decode", _p(image), chunk_stride, nclients, S, first, first_step, _p(g16), g16.numel(), _p(g32),
+         g32.numel(), DP_LAYOUTS[layout], _p(out), out_stride, k, _s())
+    _rec(ev)
+
+
 def nonfinite_flag(x, flag):
     call("mf_nonfinite_flag", _p(x), x.numel(), int(x.dtype == torch.float16), _p(flag), _s())

@@ -696,10 +696,11 @@ class MaPLeFederated(TrainerX):
         return {"clip": clip if clip > 0.0 else None, "z": z, "std": std, "delta": delta, "seed": seed}
 
     def _compress_cfg(self, get):
-        """FED.COMPRESS, COMPRESS_ROUNDING, COMPRESS_ERROR_FEEDBACK and COMPRESS_SEED, validated: {"compress": "int8" or
-        None, "rounding", "error_feedback", "seed"}.  ValueError naming the key for an unknown name, a flag that is no
-        bool, a seed outside [0, 2**64) other than -1, and FED.COMPRESS together with FED.DP_CLIP."""
-        from .federated import COMPRESS, COMPRESS_ROUNDINGS
+        """FED.COMPRESS, COMPRESS_ROUNDING, COMPRESS_ERROR_FEEDBACK and COMPRESS_SEED, validated: {"compress": "int8",
+        "topk" or None, "rounding", "error_feedback", "seed"}, and under "topk" also "k" (FED.COMPRESS_TOPK).  ValueError
+        naming the key for an unknown name, a flag that is no bool, a seed outside [0, 2**64) other than -1, a k outside
+        1..64, FED.COMPRESS together with FED.DP_CLIP, and "topk" with stochastic rounding or FED.ROBUST_AGG."""
+        from .federated import COMPRESS, COMPRESS_ROUNDINGS, TOPK_MAX
         name = get("COMPRESS", "none")
         if not isinstance(name, str) or name.strip().lower() not in ("none",) + COMPRESS:
             raise ValueError(f'FED.COMPRESS {name!r}: "none" or one of {COMPRESS}')
@@ -721,7 +722,20 @@ class MaPLeFederated(TrainerX):
             if isinstance(clip, (int, float)) and not isinstance(clip, bool) and clip > 0.0:
                 raise ValueError(f"FED.COMPRESS {name!r}: not with FED.DP_CLIP {clip:g} (a quantised, fed-back update no "
                                  "longer has an L2 norm within the bound)")
-        return {"compress": None if name == "none" else name, "rounding": rounding, "error_feedback": ef, "seed": seed}
+        out = {"compress": None if name == "none" else name, "rounding": rounding, "error_feedback": ef, "seed": seed}
+        k = get("COMPRESS_TOPK", 8)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+            raise ValueError(f"FED.COMPRESS_TOPK {k!r}: an integer from 1 to {TOPK_MAX}")
+        if name == "topk":
+            if rounding == "stochastic":
+                raise ValueError('FED.COMPRESS_ROUNDING "stochastic": not with FED.COMPRESS "topk" (the kept values travel '
+                                 "as fp32, there is nothing to round)")
+            robust = get("ROBUST_AGG", "none")
+            if isinstance(robust, str) and robust.strip().lower() != "none":
+                raise ValueError(f'FED.ROBUST_AGG {robust!r}: not with FED.COMPRESS "topk" (most coordinates of every '
+                                 "client decode to the global weights themselves)")
+            out["k"] = k
+        return out
 
     def _dyn_cfg(self, get, mu, server_opt, robust):
         """FED.DYN_ALPHA, validated: alpha, 0.0 = off.  ValueError for a value that is no number, non-finite or < 0,
@@ -756,9 +770,12 @@ class MaPLeFederated(TrainerX):
             return
         x, fed = self.exchange, self.fed[0]
         plain, wire = 4 * fed.buf.numel(), x.world * x.chunk
-        how = cp["rounding"] + (", error feedback" if cp["error_feedback"] else ", no error feedback")
-        line = (f"[INFO] FedAvg uplink compression int8 ({how}): {wire} bytes per client and round instead of {plain} "
-                f"({plain / wire:.2f}x), the downlink stays fp32")
+        if cp["compress"] == "topk":
+            how = f"k = {cp['k']} of 256" + (", error feedback" if cp["error_feedback"] else ", no error feedback")
+        else:
+            how = cp["rounding"] + (", error feedback" if cp["error_feedback"] else ", no error feedback")
+        line = (f"[INFO] FedAvg uplink compression {cp['compress']} ({how}): {wire} bytes per client and round instead "
+                f"of {plain} ({plain / wire:.2f}x), the downlink stays fp32")
         if not x.sharded:
             line += "; this exchange decodes locally (one process or \"allreduce\"): simulated, no traffic is saved"
         print(line)
@@ -790,8 +807,8 @@ class MaPLeFederated(TrainerX):
         FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
         FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
         (coordinate-wise median / trimmed mean, Yin et al.), FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
-        McMahan et al. 2018), FED.COMPRESS (int8 uplink compression with error feedback, Alistarh et al.) and
-        FED.DYN_ALPHA (FedDyn, Acar et al.)."""
+        McMahan et al. 2018), FED.COMPRESS (int8 or top-k uplink compression with error feedback, Alistarh et al.;
+        Stich et al.) and FED.DYN_ALPHA (FedDyn, Acar et al.)."""
         global_classnames = list(self.lab2cname.values())
         get = self.cfg.FED.get if hasattr(self.cfg.FED, "get") else (lambda k, d: d)
         mu = float(get("PROX_MU", 0.0))
@@ -827,7 +844,7 @@ class MaPLeFederated(TrainerX):
                                  server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"],
                                  compress=cp["compress"], compress_rounding=cp["rounding"],
                                  error_feedback=cp["error_feedback"], compress_seed=cp["seed"], client=c.client_id,
-                                 dyn=self.dyn)
+                                 dyn=self.dyn, compress_k=cp.get("k", 8))
                     for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k, dp_std=self.dp["std"],
                                        dp_seed=self.dp["seed"])
