@@ -127,7 +127,10 @@ is sent whole (e' = 0) or stays whole in the residual (e' = u), and the receiver
 global copy (mf_topk_select, mf_topk_decode).  The blocks start at coordinate 0 whatever the world size, so every layout
 gives the same bits.  Not with stochastic rounding (there is nothing to round), not with the robust aggregation (most
 coordinates of every client decode to g itself, so a median returns g unless half the clients kept the coordinate), and,
-as int8, not with dp_clip / dp_std or dyn.
+as int8, not with dp_clip / dp_std or dyn.  The two codecs are one encode and one decode kernel body with a codec each
+(csrc/compress.hip) behind one pair of wrappers (ops.py), and FedAvgExchange's constructor is the one place here that
+tells them apart: it keeps the chunk size and the two kernels with the arguments of their own, and pack(),
+decode_local() and the sharded chain make one call each.
 
 FedDyn (FedAvgBucket dyn= / FedDynState; FED.DYN_ALPHA, off by default): the dynamic regularisation of Acar, Zhao, Matas
 Navarro, Mattina, Whatmough and Saligrama (ICLR 2021), which makes the clients' local optima agree with the global one
@@ -393,11 +396,12 @@ class FedAvgBucket:
     sample-weighted layout and kernels (module docstring); None is the reference's plain mean.  `robust`
     ("median" | "trimmed_mean", with `trim_k` values cut at either end) selects the robust aggregation instead.
     `dp_clip` (finite, > 0) clips the client's update against the global copy to that L2 norm before it is packed, in
-    whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8") sends the update as int8 codes
-    with block scales instead (module docstring): `compress_rounding` "nearest" | "stochastic", `error_feedback` keeps
-    the rounding error as a per-client residual (state_dict() / load_state_dict() carry it), `compress_seed` and
-    `client`, the global client index, select the stochastic rounding's bits; `compress` "topk" sends the `compress_k`
-    (1..64) entries of largest magnitude of every block of 256 coordinates instead, with the same residual.  `dyn` (the
+    whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8" | "topk") sends the update
+    compressed instead (module docstring), and `error_feedback` keeps what did not travel as a per-client residual
+    (state_dict() / load_state_dict() carry it).  "int8": int8 codes with block scales, `compress_rounding` "nearest" |
+    "stochastic", `compress_seed` and `client`, the global client index, selecting the stochastic rounding's bits.
+    "topk": the `compress_k` (1..64) entries of largest magnitude of every block of 256 coordinates.  The bucket does not
+    tell the two apart: its pack() asks its exchange to encode, which chose the codec when it was built.  `dyn` (the
     process's FedDynState) selects FedDyn (module docstring): the bucket keeps its client's correction `lam` and unpack()
     runs the round's end; not with weight, robust, dp_clip, compress or server.
 
@@ -511,7 +515,7 @@ class FedAvgBucket:
     def pack(self, failed: bool = False):
         """Validity scan + pack.  failed=True: the client's local training raised (its weights are
         excluded, trainers/maple_fed.py:262-265); an invalid client contributes zeros and no vote
-        (:272-277).  With compress the pack is the quantiser: it writes this client's chunks of the exchange's send
+        (:272-277).  With compress the pack is the exchange's encoder: it writes this client's chunks of the exchange's send
         image and the next residual, and the fp32 bucket is filled by the decode."""
         e = self.e
         self.failed = failed
@@ -522,19 +526,13 @@ class FedAvgBucket:
             self.k.nonfinite_flag(e.flat16, self.flag)
             self.k.nonfinite_flag(e.flat32, self.flag)
         if self.compress is not None:
-            # the update against the weights the round started from, as int8 codes and block scales straight into
-            # the exchange's send image; e is read, e' written: a late-failure re-pack reads the same e, weights,
-            # global copy and round and reproduces the codes, and unpack() commits e' once
+            # the update against the weights the round started from, in the exchange's codec straight into its send
+            # image; e is read, e' written: a late-failure re-pack reads the same e, weights, global copy and round
+            # and reproduces the chunks, and unpack() commits e' once
             if self._wire is None:
                 self.exchange  # this bucket alone: its exchange owns the image
             x, slot = self._wire
-            if self.compress == "topk":  # ... or as the k largest entries of every block, (index, fp32 value)
-                self.k.topk_select(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
-                                   self.flag, self.weight, self.compress_k, x.image, slot, x.S)
-            else:
-                self.k.compress_quantize(e.flat16, e.flat32, self.global16, self.global32, self.resid, self.resid_next,
-                                         self.flag, self.weight, self.compress_rounding, self.compress_seed, x.round,
-                                         self.client, x.image, slot, x.S)
+            x.encode(self, slot)
             self._resid_due = self.resid is not None and not failed
         elif self.dp_clip is not None and not failed:
             # the update against the weights the round started from, its clip scale left on the device for the pack
@@ -684,7 +682,9 @@ class FedAvgBucket:
 
 
 class FedAvgExchange:
-    """The exchange of one rank's buckets (its C clients, in client order) with every other rank's."""
+    """The exchange of one rank's buckets (its C clients, in client order) with every other rank's.  With compress it
+    owns the uint8 send image and the codec: the constructor picks, once, the chunk size and the encode and decode
+    kernels of "int8" or "topk", and encode(), decode_local() and the sharded chain call what it picked."""
 
     def __init__(self, buckets: Sequence[FedAvgBucket], group: Optional[dist.ProcessGroup] = None,
                  mode: str = "ordered", shard_single: bool = False, robust: Optional[str] = None, trim_k: int = 1,
@@ -730,7 +730,7 @@ class FedAvgExchange:
         self.sharded = self.distributed and mode == "ordered"
         self.side = None
         self.host_stage = False
-        # int8 compression of the uplink: one setting per exchange; the uint8 send image [dest rank][client][chunk] the
+        # compression of the uplink: one setting per exchange; the uint8 send image [dest rank][client][chunk] the
         # buckets' packs write into, and under the sharded chain the image the all_to_all fills
         self.compress = b0.compress
         self.image = self.recv_image = self.topk = None
@@ -739,9 +739,19 @@ class FedAvgExchange:
                 raise ValueError("FedAvg compress: two buckets of one exchange carry the same client index (their "
                                  "rounding bits would coincide)")
             self.layout = "robust" if b0.robust is not None else ("plain" if b0.weight is None else "weighted")
-            self.topk = b0.compress_k if self.compress == "topk" else None
-            self.chunk = (self.k.compress_chunk_bytes(self.S) if self.topk is None
-                          else self.k.topk_chunk_bytes(self.S, self.topk))
+            # the one place that tells the codecs apart: the chunk size, the encode and decode kernels, and the
+            # arguments each takes of its own (encode: after the weight, from the bucket; decode: last)
+            kn = self.k
+            if self.compress == "topk":
+                self.topk = b0.compress_k
+                self.chunk = kn.topk_chunk_bytes(self.S, self.topk)
+                self._encode, self._encode_args = kn.topk_select, lambda x: (self.topk,)
+                self._decode, self._decode_args = kn.topk_decode, (self.topk,)
+            else:
+                self.chunk = kn.compress_chunk_bytes(self.S)
+                self._encode = kn.compress_quantize
+                self._encode_args = lambda x: (x.compress_rounding, x.compress_seed, self.round, x.client)
+                self._decode, self._decode_args = kn.compress_decode, ()
             self.image = torch.zeros(self.world, self.C, self.chunk, device=dev, dtype=torch.uint8)
             if self.sharded:
                 self.recv_image = torch.empty(self.world * self.C * self.chunk, device=dev, dtype=torch.uint8)
@@ -777,18 +787,21 @@ class FedAvgExchange:
             self.stage[:, j, :].copy_(x.pbuf.view(self.world, self.S))
         return self.stage.view(-1)
 
+    def encode(self, x: FedAvgBucket, slot: int):
+        """Bucket x's pack under compression: its update and the tail, in this exchange's codec, into its chunks
+        image[:, slot, :] of the send image, and its next residual."""
+        e = x.e
+        self._encode(e.flat16, e.flat32, x.global16, x.global32, x.resid, x.resid_next, x.flag, x.weight,
+                     *self._encode_args(x), self.image, slot, self.S)
+
     def decode_local(self):
         """Compressed, without the sharded chain (one process, "allreduce"): every local bucket's chunks decoded into
-        its own fp32 bucket, g + scale * q in the bucket's layout, which the existing paths then consume.  No traffic
-        is saved here: the compression is simulated."""
+        its own fp32 bucket, g + what travelled in the bucket's layout, which the existing paths then consume.  No
+        traffic is saved here: the compression is simulated."""
         img = self.image.view(-1)
         for j, x in enumerate(self.b):
-            if self.topk is not None:
-                self.k.topk_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
-                                   x.global16, x.global32, self.layout, x.pbuf, self.S, self.topk)
-            else:
-                self.k.compress_decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S,
-                                       x.global16, x.global32, self.layout, x.pbuf, self.S)
+            self._decode(img[j * self.chunk:], self.world, self.C * self.chunk, self.S, 0, self.S, x.global16,
+                         x.global32, self.layout, x.pbuf, self.S, *self._decode_args)
 
     def _local_sum(self) -> torch.Tensor:
         """The rank's buckets summed in client order (== torch.stack(...) order over these clients)."""
@@ -838,29 +851,18 @@ class FedAvgExchange:
         under gloo it is a host wait, and with device buckets (host_stage) the collectives move host copies.
         Returns the all_gather's work handle (None when it completed here)."""
         hs = self.host_stage
-        if self.compress is None:
-            recv = torch.empty(self.recv.numel(), dtype=torch.float32) if hs else self.recv
-            a2a = dist.all_to_all_single(recv, send.cpu() if hs else send, group=self.group, async_op=True)
-            a2a.wait()
-            if hs:
-                self.recv.copy_(recv)
-        else:
-            # the uint8 image moves; the receiver rebuilds the fp32 image g + scale * q of its shard of every client
-            # from the global copy every rank holds, and the rest of the chain reads it as it reads a received one
-            rimg = torch.empty(self.recv_image.numel(), dtype=torch.uint8) if hs else self.recv_image
-            a2a = dist.all_to_all_single(rimg, send.cpu() if hs else send, group=self.group, async_op=True)
-            a2a.wait()
-            if hs:
-                self.recv_image.copy_(rimg)
+        into = self.recv if self.compress is None else self.recv_image  # the fp32 image, or the uint8 one
+        recv = torch.empty(into.numel(), dtype=into.dtype) if hs else into
+        a2a = dist.all_to_all_single(recv, send.cpu() if hs else send, group=self.group, async_op=True)
+        a2a.wait()
+        if hs:
+            into.copy_(recv)
+        if self.compress is not None:
+            # the uint8 image moved; the receiver rebuilds the fp32 image g + what travelled of its shard of every
+            # client from the global copy every rank holds, and the rest of the chain reads it as a received one
             b0 = self.b[0]
-            if self.topk is not None:
-                self.k.topk_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
-                                   dist.get_rank(self.group) * self.S, 0, b0.global16, b0.global32, self.layout,
-                                   self.recv, self.S, self.topk)
-            else:
-                self.k.compress_decode(self.recv_image, self.world * self.C, self.chunk, self.S,
-                                       dist.get_rank(self.group) * self.S, 0, b0.global16, b0.global32, self.layout,
-                                       self.recv, self.S)
+            self._decode(self.recv_image, self.world * self.C, self.chunk, self.S, dist.get_rank(self.group) * self.S,
+                         0, b0.global16, b0.global32, self.layout, self.recv, self.S, *self._decode_args)
         if self.trim is None:
             self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
         else:  # the robust statistic of this rank's shard; the vote element, if it lies in this shard, counts

@@ -1074,104 +1074,17 @@ def dp_add_noise(buf, offset, seed, round_, std):
     _rec(ev)
 
 
-COMPRESS_BLOCK = 256  # coordinates per quantisation block: one fp32 scale each
+COMPRESS_BLOCK = 256  # coordinates per block of either uplink codec: one fp32 scale (int8), k kept entries (top-k)
 COMPRESS_ROUNDINGS = {"nearest": 0, "stochastic": 1}
+TOPK_MAX = 64  # entries kept per block of COMPRESS_BLOCK coordinates, at most: one lane each
+TOPK_LAYOUTS = ("plain", "weighted")
 
 
-def compress_chunk_bytes(S: int) -> int:
-    """Bytes of one wire chunk of shard length S: [S int8 codes | S / 256 fp32 scales | fp32 weight | fp32 vote]
-    (mf_compress_chunk_bytes)."""
+def _check_shard(S) -> int:
     S = int(S)
     if S <= 0 or S % COMPRESS_BLOCK:
         raise ValueError(f"S: a positive multiple of {COMPRESS_BLOCK} required, got {S}")
-    return int(call("mf_compress_chunk_bytes", S))
-
-
-def compress_quantize(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, rounding, seed, round_, client, image,
-                      slot, S):
-    """The int8 codes, block scales and tail of the update [p16 | p32] - [g16 | g32] (+ e_in, the residual; e_out
-    receives the new one; both None: no error feedback) written into image[:, slot, :], the exchange's uint8 send image
-    [destination rank][local client][compress_chunk_bytes(S)] (mf_compress_quantize, include/mapfed.h).  rounding:
-    "nearest" or "stochastic" (bits from (seed, round_, client, coordinate) alone); weight: the tail's weight (None: 1)."""
-    import math
-    if rounding not in COMPRESS_ROUNDINGS:
-        raise ValueError(f"rounding: one of {tuple(COMPRESS_ROUNDINGS)}, got {rounding!r}")
-    weight = 1.0 if weight is None else float(weight)
-    if not math.isfinite(weight) or weight <= 0.0:
-        raise ValueError(f"weight: finite and > 0 required, got {weight}")
-    seed, round_, client, slot, S = int(seed), int(round_), int(client), int(slot), int(S)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed: 0 to 2**64 - 1 required, got {seed}")
-    if not 0 <= round_ < 2 ** 32:
-        raise ValueError(f"round: 0 to 2**32 - 1 required, got {round_}")
-    if not 0 <= client < 2 ** 31:
-        raise ValueError(f"client: 0 to 2**31 - 1 required, got {client}")
-    _check_dp_pairs(p16, g16, p32, g32)
-    n = p16.numel() + p32.numel()
-    chunk = compress_chunk_bytes(S)
-    if image.dtype != torch.uint8 or image.dim() != 3 or not image.is_contiguous() or image.shape[2] != chunk:
-        raise ValueError(f"image: contiguous uint8 [ranks][clients][{chunk}] required, got {image.dtype} "
-                         f"{tuple(image.shape)}")
-    world, C = image.shape[0], image.shape[1]
-    if not 0 <= slot < C:
-        raise ValueError(f"slot: 0 to {C - 1} required, got {slot}")
-    if world * S < n:
-        raise ValueError(f"image: {world} shards of {S} hold fewer than the {n} coordinates")
-    if (e_in is None) != (e_out is None):
-        raise ValueError("e_in / e_out: both residual buffers or neither")
-    if e_in is not None:
-        _check_flat("e_in", e_in, torch.float32, n)
-        _check_flat("e_out", e_out, torch.float32, n)
-        if _overlap(e_in, e_out):
-            raise ValueError("e_out: a buffer of its own required (it overlaps e_in)")
-    if invalid_flag is None or invalid_flag.dtype != torch.int32 or invalid_flag.numel() < 1:
-        raise ValueError("invalid_flag: an int32 tensor required")
-    for oname, o in (("p16", p16), ("g16", g16), ("p32", p32), ("g32", g32), ("e_in", e_in), ("e_out", e_out)):
-        if _overlap(image, o):
-            raise ValueError(f"image: a buffer of its own required (it overlaps {oname})")
-    # weights, global copy and residual read, the residual and the chunks written
-    ev = _hbm("compress_quantize", p16.numel() * 4.0 + p32.numel() * 8.0 + (8.0 * n if e_in is not None else 0.0)
-              + world * float(chunk))
-    call("mf_compress_quantize", _p(p16), _p(g16), p16.numel(), _p(p32), _p(g32), p32.numel(), _p(e_in), _p(e_out),
-         _p(invalid_flag), weight, COMPRESS_ROUNDINGS[rounding], seed, round_, client,
-         image.data_ptr() + slot * chunk, C * chunk, S, world, _s())
-    _rec(ev)
-
-
-def compress_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride):
-    """nclients wire chunks, image[c * chunk_stride:] (a flat uint8 tensor, bytes), decoded into out[c * out_stride:
-    c * out_stride + S] (fp32): chunk c holds the global coordinates first + c * first_step + j, j < S, and out
-    receives the fp32 image the reduce kernels read, in layout "plain", "weighted" or "robust" (mf_compress_decode,
-    include/mapfed.h).  g16 / g32: the global copy the update was taken against."""
-    if layout not in DP_LAYOUTS:
-        raise ValueError(f"layout: one of {tuple(DP_LAYOUTS)}, got {layout!r}")
-    nclients, chunk_stride, S, first, first_step, out_stride = (int(v) for v in (nclients, chunk_stride, S, first,
-                                                                                  first_step, out_stride))
-    chunk = compress_chunk_bytes(S)
-    if nclients < 1 or first < 0 or first_step < 0:
-        raise ValueError(f"nclients >= 1, first >= 0 and first_step >= 0 required, got {nclients}, {first}, {first_step}")
-    if chunk_stride % 4 or (nclients > 1 and (chunk_stride < chunk or out_stride < S)):
-        raise ValueError(f"chunk_stride: a multiple of 4 of at least {chunk} bytes, and out_stride at least {S}, "
-                         f"required, got {chunk_stride}, {out_stride}")
-    if image.dtype != torch.uint8 or not image.is_contiguous() or image.numel() < (nclients - 1) * chunk_stride + chunk:
-        raise ValueError(f"image: contiguous uint8 of at least {(nclients - 1) * chunk_stride + chunk} bytes required, "
-                         f"got {image.dtype} {tuple(image.shape)}")
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < (nclients - 1) * out_stride + S:
-        raise ValueError(f"out: contiguous fp32 of at least {(nclients - 1) * out_stride + S} floats required, got "
-                         f"{out.dtype} {tuple(out.shape)}")
-    _check_flat("g16", g16, torch.float16)
-    _check_flat("g32", g32, torch.float32)
-    for oname, o in (("image", image), ("g16", g16), ("g32", g32)):
-        if _overlap(out, o):
-            raise ValueError(f"out: a buffer of its own required (it overlaps {oname})")
-    ev = _hbm("compress_decode", nclients * (float(chunk) + 4.0 * S + 3.0 * S))  # chunk and g read, the image written
-    call("mf_compress_decode", _p(image), chunk_stride, nclients, S, first, first_step, _p(g16), g16.numel(), _p(g32),
-         g32.numel(), DP_LAYOUTS[layout], _p(out), out_stride, _s())
-    _rec(ev)
-
-
-TOPK_MAX = 64  # entries kept per block of COMPRESS_BLOCK coordinates, at most: one lane each
-TOPK_LAYOUTS = ("plain", "weighted")
+    return S
 
 
 def _check_topk(k) -> int:
@@ -1180,21 +1093,23 @@ def _check_topk(k) -> int:
     return k
 
 
+def compress_chunk_bytes(S: int) -> int:
+    """Bytes of one wire chunk of shard length S: [S int8 codes | S / 256 fp32 scales | fp32 weight | fp32 vote]
+    (mf_compress_chunk_bytes)."""
+    return int(call("mf_compress_chunk_bytes", _check_shard(S)))
+
+
 def topk_chunk_bytes(S: int, k: int) -> int:
     """Bytes of one top-k wire chunk of shard length S: [S / 256 * k fp32 values | S / 256 * k uint8 indices | zero
     bytes to a multiple of 4 | fp32 weight | fp32 vote] (mf_topk_chunk_bytes)."""
-    S, k = int(S), _check_topk(k)
-    if S <= 0 or S % COMPRESS_BLOCK:
-        raise ValueError(f"S: a positive multiple of {COMPRESS_BLOCK} required, got {S}")
-    return int(call("mf_topk_chunk_bytes", S, k))
+    k = _check_topk(k)
+    return int(call("mf_topk_chunk_bytes", _check_shard(S), k))
 
 
-def topk_select(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, k, image, slot, S):
-    """The k entries of largest magnitude of every block of 256 coordinates of the update [p16 | p32] - [g16 | g32]
-    (+ e_in, the residual; e_out receives the new one, zero where a coordinate was sent; both None: no error feedback),
-    as (uint8 index, fp32 value), and the tail, written into image[:, slot, :], the exchange's uint8 send image
-    [destination rank][local client][topk_chunk_bytes(S, k)] (mf_topk_select, include/mapfed.h).  weight: the tail's
-    weight (None: 1)."""
+def _uplink_encode(key, symbol, chunk, codec_args, p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, image, slot,
+                   S):
+    """What compress_quantize and topk_select share: the checks, the byte model and the call.  chunk: the codec's wire
+    chunk for shard length S; codec_args: the codec's own arguments, which the entry point takes after the weight."""
     import math
     weight = 1.0 if weight is None else float(weight)
     if not math.isfinite(weight) or weight <= 0.0:
@@ -1202,7 +1117,6 @@ def topk_select(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, k, image,
     slot, S = int(slot), int(S)
     _check_dp_pairs(p16, g16, p32, g32)
     n = p16.numel() + p32.numel()
-    chunk = topk_chunk_bytes(S, k)
     if image.dtype != torch.uint8 or image.dim() != 3 or not image.is_contiguous() or image.shape[2] != chunk:
         raise ValueError(f"image: contiguous uint8 [ranks][clients][{chunk}] required, got {image.dtype} "
                          f"{tuple(image.shape)}")
@@ -1224,22 +1138,21 @@ def topk_select(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, k, image,
         if _overlap(image, o):
             raise ValueError(f"image: a buffer of its own required (it overlaps {oname})")
     # weights, global copy and residual read, the residual and the chunks written
-    ev = _hbm("topk_select", p16.numel() * 4.0 + p32.numel() * 8.0 + (8.0 * n if e_in is not None else 0.0)
+    ev = _hbm(key, p16.numel() * 4.0 + p32.numel() * 8.0 + (8.0 * n if e_in is not None else 0.0)
               + world * float(chunk))
-    call("mf_topk_select", _p(p16), _p(g16), p16.numel(), _p(p32), _p(g32), p32.numel(), _p(e_in), _p(e_out),
-         _p(invalid_flag), weight, k, image.data_ptr() + slot * chunk, C * chunk, S, world, _s())
+    call(symbol, _p(p16), _p(g16), p16.numel(), _p(p32), _p(g32), p32.numel(), _p(e_in), _p(e_out),
+         _p(invalid_flag), weight, *codec_args, image.data_ptr() + slot * chunk, C * chunk, S, world, _s())
     _rec(ev)
 
 
-def topk_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride, k):
-    """nclients top-k wire chunks, image[c * chunk_stride:] (a flat uint8 tensor, bytes), decoded into
-    out[c * out_stride: c * out_stride + S] (fp32) as compress_decode does: g plus the sent value at a kept coordinate,
-    g + 0 elsewhere, in layout "plain" or "weighted" (mf_topk_decode, include/mapfed.h)."""
-    if layout not in TOPK_LAYOUTS:
-        raise ValueError(f"layout: one of {TOPK_LAYOUTS}, got {layout!r}")
+def _uplink_decode(key, symbol, chunk, layouts, codec_args, image, nclients, chunk_stride, S, first, first_step, g16,
+                   g32, layout, out, out_stride):
+    """What compress_decode and topk_decode share.  layouts: the ones the codec's decode knows; codec_args: the
+    codec's own arguments, which the entry point takes last."""
+    if layout not in layouts:
+        raise ValueError(f"layout: one of {tuple(layouts)}, got {layout!r}")
     nclients, chunk_stride, S, first, first_step, out_stride = (int(v) for v in (nclients, chunk_stride, S, first,
                                                                                   first_step, out_stride))
-    chunk = topk_chunk_bytes(S, k)
     if nclients < 1 or first < 0 or first_step < 0:
         raise ValueError(f"nclients >= 1, first >= 0 and first_step >= 0 required, got {nclients}, {first}, {first_step}")
     if chunk_stride % 4 or (nclients > 1 and (chunk_stride < chunk or out_stride < S)):
@@ -1256,10 +1169,57 @@ def topk_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, l
     for oname, o in (("image", image), ("g16", g16), ("g32", g32)):
         if _overlap(out, o):
             raise ValueError(f"out: a buffer of its own required (it overlaps {oname})")
-    ev = _hbm("topk_decode", nclients * (float(chunk) + 4.0 * S + 3.0 * S))  # chunk and g read, the image written
-    call("mf_topk_decode", _p(image), chunk_stride, nclients, S, first, first_step, _p(g16), g16.numel(), _p(g32),
-         g32.numel(), DP_LAYOUTS[layout], _p(out), out_stride, k, _s())
+    ev = _hbm(key, nclients * (float(chunk) + 4.0 * S + 3.0 * S))  # chunk and g read, the image written
+    call(symbol, _p(image), chunk_stride, nclients, S, first, first_step, _p(g16), g16.numel(), _p(g32), g32.numel(),
+         DP_LAYOUTS[layout], _p(out), out_stride, *codec_args, _s())
     _rec(ev)
+
+
+def compress_quantize(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, rounding, seed, round_, client, image,
+                      slot, S):
+    """The int8 codes, block scales and tail of the update [p16 | p32] - [g16 | g32] (+ e_in, the residual; e_out
+    receives the new one; both None: no error feedback) written into image[:, slot, :], the exchange's uint8 send image
+    [destination rank][local client][compress_chunk_bytes(S)] (mf_compress_quantize, include/mapfed.h).  rounding:
+    "nearest" or "stochastic" (bits from (seed, round_, client, coordinate) alone); weight: the tail's weight (None: 1)."""
+    if rounding not in COMPRESS_ROUNDINGS:
+        raise ValueError(f"rounding: one of {tuple(COMPRESS_ROUNDINGS)}, got {rounding!r}")
+    seed, round_, client = int(seed), int(round_), int(client)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed: 0 to 2**64 - 1 required, got {seed}")
+    if not 0 <= round_ < 2 ** 32:
+        raise ValueError(f"round: 0 to 2**32 - 1 required, got {round_}")
+    if not 0 <= client < 2 ** 31:
+        raise ValueError(f"client: 0 to 2**31 - 1 required, got {client}")
+    _uplink_encode("compress_quantize", "mf_compress_quantize", compress_chunk_bytes(S),
+                   (COMPRESS_ROUNDINGS[rounding], seed, round_, client), p16, p32, g16, g32, e_in, e_out, invalid_flag,
+                   weight, image, slot, S)
+
+
+def compress_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride):
+    """nclients wire chunks, image[c * chunk_stride:] (a flat uint8 tensor, bytes), decoded into out[c * out_stride:
+    c * out_stride + S] (fp32): chunk c holds the global coordinates first + c * first_step + j, j < S, and out
+    receives the fp32 image the reduce kernels read, in layout "plain", "weighted" or "robust" (mf_compress_decode,
+    include/mapfed.h).  g16 / g32: the global copy the update was taken against."""
+    _uplink_decode("compress_decode", "mf_compress_decode", compress_chunk_bytes(S), DP_LAYOUTS, (), image, nclients,
+                   chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride)
+
+
+def topk_select(p16, p32, g16, g32, e_in, e_out, invalid_flag, weight, k, image, slot, S):
+    """The k entries of largest magnitude of every block of 256 coordinates of the update [p16 | p32] - [g16 | g32]
+    (+ e_in, the residual; e_out receives the new one, zero where a coordinate was sent; both None: no error feedback),
+    as (uint8 index, fp32 value), and the tail, written into image[:, slot, :], the exchange's uint8 send image
+    [destination rank][local client][topk_chunk_bytes(S, k)] (mf_topk_select, include/mapfed.h).  weight: the tail's
+    weight (None: 1)."""
+    _uplink_encode("topk_select", "mf_topk_select", topk_chunk_bytes(S, k), (k,), p16, p32, g16, g32, e_in, e_out,
+                   invalid_flag, weight, image, slot, S)
+
+
+def topk_decode(image, nclients, chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride, k):
+    """nclients top-k wire chunks, image[c * chunk_stride:] (a flat uint8 tensor, bytes), decoded into
+    out[c * out_stride: c * out_stride + S] (fp32) as compress_decode does: g plus the sent value at a kept coordinate,
+    g + 0 elsewhere, in layout "plain" or "weighted" (mf_topk_decode, include/mapfed.h)."""
+    _uplink_decode("topk_decode", "mf_topk_decode", topk_chunk_bytes(S, k), TOPK_LAYOUTS, (k,), image, nclients,
+                   chunk_stride, S, first, first_step, g16, g32, layout, out, out_stride)
 
 
 def nonfinite_flag(x, flag):

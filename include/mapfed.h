@@ -501,33 +501,34 @@ int mf_compress_decode(const void* image, int64_t chunk_stride, int nclients, in
                        int64_t first_step, const void* g16, int64_t n16, const float* g32, int64_t n32, int layout,
                        float* out, int64_t out_stride, void* stream);
 /* ---- block-wise top-k sparsification of the FedAvg uplink with error feedback (Aji & Heafield, EMNLP 2017; Stich,
- * Cordonnier, Jaggi, NeurIPS 2018; Lin et al., ICLR 2018; Sattler et al. 2019).  Coordinates, blocks of B = 256, the
- * padding and the rules above (one IEEE operation at a time, no float atomics, plain vector stores, every check before
- * any launch) are those of the int8 pair.  1 <= k <= 64.
+ * Cordonnier, Jaggi, NeurIPS 2018; Lin et al., ICLR 2018; Sattler et al. 2019): the second codec of the same exchange.
+ * What the int8 pair states above holds here unchanged and is written once in the code (csrc/compress.hip): the
+ * coordinates, the blocks of B = 256 and the padding; the update u_i = d_i + e_i, or d_i without a residual; the
+ * residual's two buffers; the invalid client (an all-zero payload, weight 0, vote 0, e' = e, no weight read); the
+ * {weight, vote} tail that closes every chunk and the `world` chunks at image + r * rank_stride; the decode's chunks,
+ * strides, first and first_step, its elements at n, n + 1 and beyond; and the rules (one IEEE operation at a time, no
+ * float atomics, plain vector stores, every check before any launch).  Only the following is this codec's.
+ * 1 <= k <= 64.
  *
- * Select: d_i = float(x_i) - float(g_i);  u_i = d_i + e_i (e_in == e_out == null: u_i = d_i, e neither read nor
- * written).  mag_i = the bits of u_i with the sign bit cleared, as an unsigned integer (a total order that places inf
- * and NaN too).  Within a block a precedes b iff mag_a > mag_b, or mag_a == mag_b and a has the lower index; the first k
+ * Select: mag_i = the bits of u_i with the sign bit cleared, as an unsigned integer (a total order that places inf and
+ * NaN too).  Within a block a precedes b iff mag_a > mag_b, or mag_a == mag_b and a has the lower index; the first k
  * are kept (an all-zero block, or one past n: the indices 0 .. k - 1 with value 0).  The kept entries travel in ascending
  * index order, each as (uint8 index within the block, fp32 u_i with its sign).  e'_i = +0 for a kept coordinate, u_i for
- * the others, written to e_out for i < n.  A client whose *invalid_flag is set writes zero bytes for every value and
- * index, weight 0 and vote 0, and copies e to e'; no weight of it is read.
+ * the others, written to e_out for i < n.
  *
- * Wire chunk per (destination rank r, client), nb = S / 256 blocks: [nb * k fp32 values | nb * k uint8 indices | zero
- * bytes up to a multiple of 4 | fp32 weight | fp32 vote], block b's entries at b * k .. b * k + k - 1 of either region:
- * mf_topk_chunk_bytes(S, k) = 4 nb k + 4 ceil(nb k / 4) + 8 bytes (-1 unless S is a positive multiple of 256 and
- * 1 <= k <= 64).  mf_topk_select writes the `world` chunks of one client at image + r * rank_stride, as
- * mf_compress_quantize does.  One wave64 per block, four coordinates per lane; the k-th largest of the 39-bit keys
- * (mag << 8) | (255 - index) is found most significant bit first, each step a count by ballot and popcount across the
- * wave; a kept coordinate's position is the count of kept coordinates before it.  Errors: those of mf_compress_quantize
- * (no rounding, no client), and k outside 1..64.
+ * Wire chunk, nb = S / 256 blocks: [nb * k fp32 values | nb * k uint8 indices | zero bytes up to a multiple of 4 | the
+ * tail], block b's entries at b * k .. b * k + k - 1 of either region: mf_topk_chunk_bytes(S, k) = 4 nb k +
+ * 4 ceil(nb k / 4) + 8 bytes (-1 unless S is a positive multiple of 256 and 1 <= k <= 64).  One wave64 per block, four
+ * coordinates per lane; the k-th largest of the 39-bit keys (mag << 8) | (255 - index) is found most significant bit
+ * first, each step a count by ballot and popcount across the wave; a kept coordinate's position is the count of kept
+ * coordinates before it.  Errors: those of mf_compress_quantize (no rounding, no client), and k outside 1..64.
  *
- * Decode: chunks, strides, first and first_step as mf_compress_decode.  s_i = the entry's value if i is a kept
- * coordinate, +0 otherwise (with a repeated index any one of its entries wins; an index is a byte and cannot leave its
- * block);  y = float(g_i) + s_i, always the one fp32 add, then w * y (layout 1) or y (layout 0); the elements at n,
- * n + 1 and beyond, and a chunk whose vote is 0, as mf_compress_decode.  Layouts 0 and 1 only.  One wave per block per
- * chunk, the entries scattered through a 1 KB tile of LDS.  Errors: those of mf_compress_decode, layout 2, and k
- * outside 1..64.                                                                                                   */
+ * Decode: s_i = the entry's value if i is a kept coordinate, +0 otherwise (with a repeated index any one of its entries
+ * wins; an index is a byte and cannot leave its block);  y = float(g_i) + s_i, always the one fp32 add, then w * y
+ * (layout 1) or y (layout 0).  Layouts 0 and 1 only, so a chunk whose vote is 0 decodes to zeros.  One wave per block
+ * per chunk, the entries scattered through a 1 KB tile of LDS.  Errors: those of mf_compress_decode, layout 2, and k
+ * outside 1..64.  In either pair a codec's own arguments (rounding and client; k) are checked ahead of the shared
+ * ones.                                                                                                            */
 int64_t mf_topk_chunk_bytes(int64_t S, int k);
 int mf_topk_select(const void* x16, const void* g16, int64_t n16, const float* x32, const float* g32, int64_t n32,
                    const float* e_in, float* e_out, const int* invalid_flag, float weight, int k, void* image,
