@@ -73,6 +73,11 @@ SIGNATURES = {
     "mf_fedavg_reduce_ordered": [P, I, L, L, P, P],
     "mf_fedavg_reduce_trimmed": [P, I, L, L, I, L, P, P],
     "mf_fedavg_pack_robust": [P, L, P, L, P, P, P],
+    "mf_krum_ws_bytes": [I, L],
+    "mf_krum_chunk_elems": [],
+    "mf_krum_pairwise": [P, I, L, L, P, P, P],
+    "mf_krum_select": [P, I, I, I, I, P, P, P, P],
+    "mf_fedavg_reduce_selected": [P, I, L, L, P, L, P, P],
     "mf_dp_update_ws_floats": [L, L],
     "mf_dp_update_scale": [P, P, L, P, P, L, F, P, P, P],
     "mf_fedavg_pack_clipped": [P, L, P, L, P, P, P, P, F, I, P, P],
@@ -97,10 +102,11 @@ SIGNATURES = {
 _VALUE_FUNCS = {"mf_abi_version", "mf_layernorm_bwd_blocks", "mf_colsum_blocks", "mf_optim_chunk_bytes",
                 "mf_optim_chunk_elems", "mf_col_reduce_desc_bytes", "mf_small_linear_desc_bytes",
                 "mf_gemm_splitk_ws_floats", "mf_augment_ws_bytes", "mf_qkv_attention_supported", "mf_dp_update_ws_floats",
-                "mf_compress_chunk_bytes", "mf_topk_chunk_bytes"}
+                "mf_compress_chunk_bytes", "mf_topk_chunk_bytes", "mf_krum_ws_bytes", "mf_krum_chunk_elems"}
 # value functions whose return type is not int
 _RESTYPES = {"mf_augment_ws_bytes": ctypes.c_int64, "mf_dp_update_ws_floats": ctypes.c_int64,
-             "mf_compress_chunk_bytes": ctypes.c_int64, "mf_topk_chunk_bytes": ctypes.c_int64}
+             "mf_compress_chunk_bytes": ctypes.c_int64, "mf_topk_chunk_bytes": ctypes.c_int64,
+             "mf_krum_ws_bytes": ctypes.c_int64}
 
 _LIB = None
 

@@ -230,7 +230,14 @@ def extend_cfg(cfg: CfgNode) -> None:
                            # Robust Distributed Learning: Towards Optimal Statistical Rates", ICML 2018): "none",
                            # "median" (coordinate-wise) or "trimmed_mean" (coordinate-wise, the TRIM_K smallest and
                            # the TRIM_K largest of the clients' values dropped; 2 * TRIM_K < NUM_CLIENTS)
+                           # ... or "multi_krum" (Blanchard et al., NeurIPS 2017; El Mhamdi et al., ICML 2018): whole
+                           # clients are kept or dropped by their squared L2 distances to their nearest peers
                            ROBUST_AGG="none", TRIM_K=1,
+                           # Multi-Krum: the number of clients tolerated as wrong; NUM_CLIENTS >= 2 * KRUM_F + 3
+                           KRUM_F=1,
+                           # Multi-Krum: the number of best-scored clients whose mean becomes the global model; 0 = all
+                           # but KRUM_F, 1 = Krum; at most NUM_CLIENTS - KRUM_F
+                           KRUM_M=0,
                            # DP-FedAvg (McMahan, Ramage, Talwar, Zhang, ICLR 2018).  DP_CLIP: the L2 bound S every
                            # client's update w_k - w_global is clipped to before it is packed; 0 = off.  On its own
                            # it is norm bounding (Sun et al., 2019) and combines with every option above

@@ -78,6 +78,21 @@ the same kernel over its buckets staged contiguously, also for a single client: 
 into a zero vote.  Not combined with "allreduce" (a sum has lost the per-client values) or with client weights (a
 weighted median is another statistic).
 
+Multi-Krum (robust="multi_krum", krum_f=1, krum_m=0; FED.ROBUST_AGG multi_krum, FED.KRUM_F, FED.KRUM_M): Blanchard, El
+Mhamdi, Guerraoui and Stainer (NeurIPS 2017), keeping the m best as El Mhamdi, Guerraoui and Rouault do (ICML 2018).  A
+coordinate-wise statistic still mixes every client into every coordinate; Multi-Krum drops whole clients.  The bucket
+and the image are the robust ones, and three kernels run in the trimmed reduce's place: mf_krum_pairwise forms the fp64
+squared distances D[i][j] of this rank's shard of every client (an absent client's NaNs make its row, column and
+diagonal NaN), one all_gather hands every rank the W partial matrices (W * N^2 doubles), mf_krum_select adds them in
+rank order, scores every present client by the sum of its p - f' - 2 smallest distances and keeps the m' best (f' and
+m' degrade with the number p of present clients, as the trim does), and mf_fedavg_reduce_selected averages the kept
+clients in client order, writing p at the vote element, so the reduced bucket again reads [statistic | 1 | p].  Given
+the selection the statistic depends on no layout; the distances' last fp64 bits do (the shard boundaries move), so two
+layouts can select differently only where two scores lie within 2 n 2^-53 of each other.  All ranks
+add the same parts in the same order and always agree.  krum_m = 1 is Krum; krum_m = 0 keeps all but f'.  Every
+exclusion of the robust aggregation holds: not with "allreduce", client weights, dp_std, topk or dyn; dp_clip, int8,
+the server optimizers and FedProx combine as with the median.
+
 DP-FedAvg (FedAvgBucket dp_clip / FedAvgExchange dp_std; FED.DP_CLIP and FED.DP_NOISE_MULTIPLIER, off by default):
 user-level differential privacy as McMahan, Ramage, Talwar and Zhang define it (ICLR 2018; Geyer et al. 2017).  Each
 client's update Delta_k = w_k - g against the round's starting weights g (the bucket's global copy) is clipped to the L2
@@ -160,8 +175,9 @@ import torch.distributed as dist
 from . import ops
 
 MODES = ("ordered", "allreduce")
-ROBUST = ("median", "trimmed_mean")
+ROBUST = ("median", "trimmed_mean", "multi_krum")
 MEDIAN_TRIM = ops.MEDIAN_TRIM  # a trim no client count reaches: the trimmed reduce degrades it to the median
+KRUM_TRIM = -1  # robust_trim's value for "multi_krum": the robust layout, no trimmed reduce
 COMPRESS = ("int8", "topk")
 TOPK_MAX = ops.TOPK_MAX  # entries kept per block of COMPRESS_BLOCK coordinates, at most
 COMPRESS_ROUNDINGS = tuple(ops.COMPRESS_ROUNDINGS)
@@ -190,21 +206,33 @@ def dp_epsilon(z: float, rounds: int, delta: float) -> float:
 
 
 def robust_trim(robust: Optional[str], trim_k: int, mode: str = "ordered", weighted: bool = False) -> Optional[int]:
-    """The trim the reduce kernel is called with (None: no robust aggregation).  ValueError for an unknown name,
-    the "allreduce" mode, client weights, or trim_k < 1 for "trimmed_mean"."""
+    """The trim the reduce kernel is called with (None: no robust aggregation; KRUM_TRIM for "multi_krum", which has
+    a reduce of its own).  ValueError for an unknown name, the "allreduce" mode, client weights, or trim_k < 1 for
+    "trimmed_mean"."""
     if robust is None:
         return None
     if robust not in ROBUST:
-        raise ValueError(f"robust aggregation {robust!r}: None or one of {ROBUST}")
+        hint = ' (Krum is "multi_krum" with krum_m = 1)' if robust == "krum" else ""
+        raise ValueError(f"robust aggregation {robust!r}: None or one of {ROBUST}{hint}")
     if mode != "ordered":
         raise ValueError(f'robust aggregation needs mode "ordered" (got {mode!r}): a sum has lost the per-client values')
     if weighted:
         raise ValueError("robust aggregation with a client weight: a weighted median is a different statistic")
     if robust == "median":
         return MEDIAN_TRIM
+    if robust == "multi_krum":
+        return KRUM_TRIM
     if isinstance(trim_k, bool) or not isinstance(trim_k, int) or not 1 <= trim_k <= MEDIAN_TRIM:
         raise ValueError(f"trimmed_mean trim_k {trim_k!r}: an integer >= 1")
     return trim_k
+
+
+def check_krum(krum_f, krum_m):
+    """Multi-Krum's f (clients tolerated as wrong) and m (clients kept; 0: all but f): integers >= 0."""
+    for label, v in (("krum_f", krum_f), ("krum_m", krum_m)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"multi_krum {label} {v!r}: an integer >= 0")
+    return krum_f, krum_m
 
 
 class FederatedAbort(RuntimeError):
@@ -223,6 +251,10 @@ class _HipKernels:
     fedopt_deliver = staticmethod(ops.fedopt_deliver)
     fedavg_pack_robust = staticmethod(ops.fedavg_pack_robust)
     fedavg_reduce_trimmed = staticmethod(ops.fedavg_reduce_trimmed)
+    krum_ws_bytes = staticmethod(ops.krum_ws_bytes)
+    krum_pairwise = staticmethod(ops.krum_pairwise)
+    krum_select = staticmethod(ops.krum_select)
+    fedavg_reduce_selected = staticmethod(ops.fedavg_reduce_selected)
     dp_update_ws_floats = staticmethod(ops.dp_update_ws_floats)
     dp_update_scale = staticmethod(ops.dp_update_scale)
     fedavg_pack_clipped = staticmethod(ops.fedavg_pack_clipped)
@@ -394,7 +426,8 @@ class FedAvgBucket:
     trainables) and after_weights_loaded().  `kernels` defaults to the HIP kernels; tests substitute host
     restatements to exercise the collective protocol on CPU ranks (gloo).  `weight` (finite, > 0) selects the
     sample-weighted layout and kernels (module docstring); None is the reference's plain mean.  `robust`
-    ("median" | "trimmed_mean", with `trim_k` values cut at either end) selects the robust aggregation instead.
+    ("median" | "trimmed_mean", with `trim_k` values cut at either end, or "multi_krum" with `krum_f` clients tolerated
+    as wrong and `krum_m` kept, 0 = all but krum_f) selects the robust aggregation instead.
     `dp_clip` (finite, > 0) clips the client's update against the global copy to that L2 norm before it is packed, in
     whichever layout the bucket has (module docstring, DP-FedAvg).  `compress` ("int8" | "topk") sends the update
     compressed instead (module docstring), and `error_feedback` keeps what did not travel as a per-client residual
@@ -414,7 +447,7 @@ class FedAvgBucket:
                  server: Optional["ServerOptimizer"] = None, robust: Optional[str] = None, trim_k: int = 1,
                  dp_clip: Optional[float] = None, compress: Optional[str] = None, compress_rounding: str = "nearest",
                  error_feedback: bool = True, compress_seed: int = 0, client: int = 0,
-                 dyn: Optional["FedDynState"] = None, compress_k: int = 8):
+                 dyn: Optional["FedDynState"] = None, compress_k: int = 8, krum_f: int = 1, krum_m: int = 0):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         if compress is not None and compress not in COMPRESS:
@@ -455,6 +488,7 @@ class FedAvgBucket:
         self.dp_clip = dp_clip
         self.trim = robust_trim(robust, trim_k, mode, weight is not None)
         self.robust, self.trim_k = robust, trim_k
+        self.krum_f, self.krum_m = check_krum(krum_f, krum_m) if robust == "multi_krum" else (krum_f, krum_m)
         if weight is not None:
             weight = float(weight)
             if not math.isfinite(weight) or weight <= 0.0:
@@ -648,7 +682,7 @@ class FedAvgBucket:
     def exchange(self) -> "FedAvgExchange":
         if self._x is None:
             self._x = FedAvgExchange([self], group=self.group, mode=self.mode, shard_single=self.shard_single,
-                                     robust=self.robust, trim_k=self.trim_k)
+                                     robust=self.robust, trim_k=self.trim_k, krum_f=self.krum_f, krum_m=self.krum_m)
         return self._x
 
     @property
@@ -688,7 +722,7 @@ class FedAvgExchange:
 
     def __init__(self, buckets: Sequence[FedAvgBucket], group: Optional[dist.ProcessGroup] = None,
                  mode: str = "ordered", shard_single: bool = False, robust: Optional[str] = None, trim_k: int = 1,
-                 dp_std: float = 0.0, dp_seed: int = 0):
+                 dp_std: float = 0.0, dp_seed: int = 0, krum_f: int = 1, krum_m: int = 0):
         if mode not in MODES:
             raise ValueError(f"FedAvg mode {mode!r}: one of {MODES}")
         dp_std = float(dp_std)
@@ -705,6 +739,11 @@ class FedAvgExchange:
         assert len({x.weight is None for x in self.b}) == 1, "weighted and unweighted buckets in one exchange"
         self.trim = robust_trim(robust, trim_k, mode, self.b[0].weight is not None)
         assert all(x.trim == self.trim for x in self.b), "the buckets and their exchange differ in robust / trim_k"
+        self.krum = robust == "multi_krum"
+        if self.krum:
+            self.krum_f, self.krum_m = check_krum(krum_f, krum_m)
+            assert all((x.krum_f, x.krum_m) == (krum_f, krum_m) for x in self.b), \
+                "the buckets and their exchange differ in krum_f / krum_m"
         b0 = self.b[0]
         if dp_std > 0.0:
             if any(x.dp_clip is None for x in self.b):
@@ -777,6 +816,18 @@ class FedAvgExchange:
         if self.trim is not None and not self.distributed:
             self.local_stage = torch.empty(self.C, padded, device=dev, dtype=torch.float32)
         self.count_pos = b0.buf.numel() - 1  # the vote element, the last of the bucket
+        # Multi-Krum: this rank's fp64 distance matrix over its coordinates, the W ranks' matrices gathered, the pairwise
+        # kernel's workspace, and the selection every rank computes identically from the same W parts
+        if self.krum:
+            nc = self.world * self.C if self.sharded else self.C
+            span = self.S if self.sharded else padded
+            self.kn = nc
+            self.kpart = torch.zeros(nc * nc, device=dev, dtype=torch.float64)
+            self.kparts = torch.zeros(self.world * nc * nc, device=dev, dtype=torch.float64) if self.sharded else None
+            self.kws = torch.zeros(-(-self.k.krum_ws_bytes(nc, span) // 8), device=dev, dtype=torch.float64)
+            self.selected = torch.zeros(nc, device=dev, dtype=torch.int32)
+            self.scores = torch.zeros(nc, device=dev, dtype=torch.float64)
+            self.kcounts = torch.zeros(3, device=dev, dtype=torch.int32)
         self.started = False
         self.work = None
 
@@ -817,6 +868,11 @@ class FedAvgExchange:
         bucket.  It runs for a single client too: it turns an invalid client's absence marks into a zero vote."""
         for j, x in enumerate(self.b):
             self.local_stage[j].copy_(x.pbuf)
+        if self.krum:  # one part: the distances over the whole bucket
+            self.k.krum_pairwise(self.local_stage.view(-1), self.C, self.local_stage.shape[1], self.kws, self.kpart)
+            self.k.krum_select(self.kpart, self.C, self.krum_f, self.krum_m, self.selected, self.scores, self.kcounts)
+            self.k.fedavg_reduce_selected(self.local_stage.view(-1), self.C, self.selected, self.count_pos, self.total)
+            return self.total
         self.k.fedavg_reduce_trimmed(self.local_stage.view(-1), self.C, self.trim, self.count_pos, self.total)
         return self.total
 
@@ -865,6 +921,20 @@ class FedAvgExchange:
                          0, b0.global16, b0.global32, self.layout, self.recv, self.S, *self._decode_args)
         if self.trim is None:
             self.k.fedavg_reduce_ordered(self.recv, self.world * self.C, self.shard)
+        elif self.krum:
+            # the distances over this rank's coordinates, every rank's part to every rank (W * N^2 doubles), the same
+            # selection on every rank from the same parts in the same order, then the mean of the kept clients
+            pos = self.count_pos - dist.get_rank(self.group) * self.S
+            self.k.krum_pairwise(self.recv, self.kn, self.S, self.kws, self.kpart)
+            if hs:
+                parts = torch.empty(self.kparts.numel(), dtype=torch.float64)
+                dist.all_gather_into_tensor(parts, self.kpart.cpu(), group=self.group)
+                self.kparts.copy_(parts)
+            else:
+                dist.all_gather_into_tensor(self.kparts, self.kpart, group=self.group, async_op=True).wait()
+            self.k.krum_select(self.kparts, self.kn, self.krum_f, self.krum_m, self.selected, self.scores, self.kcounts)
+            self.k.fedavg_reduce_selected(self.recv, self.kn, self.selected, pos if 0 <= pos < self.S else -1,
+                                          self.shard)
         else:  # the robust statistic of this rank's shard; the vote element, if it lies in this shard, counts
             pos = self.count_pos - dist.get_rank(self.group) * self.S
             self.k.fedavg_reduce_trimmed(self.recv, self.world * self.C, self.trim, pos if 0 <= pos < self.S else -1,
@@ -944,3 +1014,15 @@ class FedAvgExchange:
 
     def n_valid(self) -> int:
         return self.b[0].n_valid()
+
+    def krum_stats(self):
+        """Multi-Krum's last selection (one host sync; for logging): (the kept clients' global ids, ascending -- the
+        image's row order is the global client order --, every client's score with NaN for an absent one, p present,
+        the effective f', the number kept m')."""
+        if not self.krum:
+            raise ValueError('krum_stats: the exchange was not built with robust="multi_krum"')
+        flat = torch.cat([self.selected.double(), self.kcounts.double(), self.scores]).cpu()
+        nc = self.kn
+        kept = [c for c in range(nc) if flat[c] != 0]
+        p, fe, me = (int(v) for v in flat[nc:nc + 3])
+        return kept, flat[nc + 3:].tolist(), p, fe, me

@@ -993,6 +993,101 @@ def fedavg_pack_robust(p16, p32, invalid_flag, bucket):
     call("mf_fedavg_pack_robust", _p(p16), p16.numel(), _p(p32), p32.numel(), _p(invalid_flag), _p(bucket), _s())
 
 
+KRUM_MAX_CLIENTS = 64
+
+
+def _check_krum_clients(nclients) -> int:
+    if isinstance(nclients, bool) or int(nclients) != nclients or not 1 <= nclients <= KRUM_MAX_CLIENTS:
+        raise ValueError(f"nclients: 1 to {KRUM_MAX_CLIENTS} required, got {nclients!r}")
+    return int(nclients)
+
+
+def krum_ws_bytes(nclients: int, n: int) -> int:
+    """Bytes of workspace krum_pairwise needs for nclients rows of n coordinates (mf_krum_ws_bytes)."""
+    nclients = _check_krum_clients(nclients)
+    if int(n) != n or n < 0:
+        raise ValueError(f"n: an integer >= 0 required, got {n!r}")
+    return int(call("mf_krum_ws_bytes", nclients, int(n)))
+
+
+def krum_chunk_elems() -> int:
+    """Coordinates per workgroup of krum_pairwise's first launch."""
+    return int(call("mf_krum_chunk_elems"))
+
+
+def krum_pairwise(gathered, nclients, n, ws, dist):
+    """dist[i][j] = sum over t < n of (double)(x_i[t] - x_j[t])^2 with x = gathered.view(nclients, -1): Multi-Krum's
+    squared distances, fp32 subtract, fp64 square and sum, in a fixed order (mf_krum_pairwise; two launches, no host
+    synchronisation).  A NaN row is an absent client: its row, column and diagonal are NaN.  ws: contiguous fp64 of at
+    least krum_ws_bytes(nclients, n) bytes; dist: contiguous fp64 of nclients^2 elements; buffers of their own."""
+    nclients = _check_krum_clients(nclients)
+    if gathered.dtype != torch.float32 or not gathered.is_contiguous():
+        raise ValueError(f"gathered: contiguous fp32 required, got {gathered.dtype} {tuple(gathered.shape)}")
+    stride = gathered.numel() // nclients
+    if int(n) != n or n < 0 or gathered.numel() != stride * nclients or n > stride:
+        raise ValueError(f"gathered: {nclients} rows of at least n = {n} floats required, got {gathered.numel()}")
+    need = krum_ws_bytes(nclients, n)
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() * 8 < need:
+        raise ValueError(f"ws: contiguous fp64 of at least {need} bytes required, got {ws.dtype} {tuple(ws.shape)}")
+    _check_flat("dist", dist, torch.float64, nclients * nclients)
+    _check_same_device(gathered, (("ws", ws), ("dist", dist)))
+    for (an, a), (bn, b) in ((("ws", ws), ("gathered", gathered)), (("dist", dist), ("gathered", gathered)),
+                             (("ws", ws), ("dist", dist))):
+        if _overlap(a, b):
+            raise ValueError(f"{an}: a buffer of its own required (it overlaps {bn})")
+    ev = _hbm("krum_pairwise", nclients * int(n) * 4.0)  # the image read once (algorithmically)
+    call("mf_krum_pairwise", _p(gathered), nclients, stride, int(n), _p(ws), _p(dist), _s())
+    _rec(ev)
+
+
+def krum_select(parts, nclients, f, m, selected, scores, counts):
+    """Multi-Krum's selection from the shards' distance matrices parts ([nparts, nclients^2] fp64, added in part
+    order): selected (nclients int32, 0 / 1), scores (nclients fp64, NaN for an absent client) and counts (3 int32:
+    p present, the effective f', the number kept m') (mf_krum_select; one workgroup).  m = 0 keeps p - f' clients."""
+    nclients = _check_krum_clients(nclients)
+    for name, v in (("f", f), ("m", m)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v < 2 ** 31:
+            raise ValueError(f"{name}: an integer >= 0 required, got {v!r}")
+    nn = nclients * nclients
+    if parts.dtype != torch.float64 or not parts.is_contiguous() or parts.numel() < nn or parts.numel() % nn:
+        raise ValueError(f"parts: contiguous fp64 of nparts * {nn} elements required, got {parts.dtype} "
+                         f"{tuple(parts.shape)}")
+    _check_flat("selected", selected, torch.int32, nclients)
+    _check_flat("scores", scores, torch.float64, nclients)
+    _check_flat("counts", counts, torch.int32, 3)
+    _check_same_device(parts, (("selected", selected), ("scores", scores), ("counts", counts)))
+    outs = (("selected", selected), ("scores", scores), ("counts", counts))
+    for i, (name, t) in enumerate(outs):
+        for oname, o in (("parts", parts),) + outs[i + 1:]:
+            if _overlap(t, o):
+                raise ValueError(f"{name}: a buffer of its own required (it overlaps {oname})")
+    call("mf_krum_select", _p(parts), parts.numel() // nn, nclients, int(f), int(m), _p(selected), _p(scores),
+         _p(counts), _s())
+
+
+def fedavg_reduce_selected(gathered, nclients, selected, count_pos, out):
+    """out = the mean, in client order, of the rows of gathered.view(nclients, -1)[:, :n] whose selected[c] (int32, read
+    on the device) is non-zero, n = out.numel(); nobody selected gives +0; out[count_pos] = the number of non-NaN
+    values at that coordinate (count_pos -1: none) (mf_fedavg_reduce_selected)."""
+    nclients, count_pos = _check_krum_clients(nclients), int(count_pos)
+    for name, t in (("gathered", gathered), ("out", out)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous fp32 required, got {t.dtype} {tuple(t.shape)}")
+    stride = gathered.numel() // nclients
+    if gathered.numel() != stride * nclients or out.numel() > stride:
+        raise ValueError(f"gathered: {nclients} rows of at least {out.numel()} floats required, got {gathered.numel()}")
+    _check_flat("selected", selected, torch.int32, nclients)
+    if count_pos >= out.numel():
+        raise ValueError(f"count_pos: below {out.numel()} (or -1) required, got {count_pos}")
+    _check_same_device(gathered, (("selected", selected), ("out", out)))
+    if _overlap(gathered, out):
+        raise ValueError("out: a buffer of its own required (it overlaps gathered)")
+    ev = _hbm("fedavg_reduce_selected", (nclients + 1) * out.numel() * 4.0)  # at most: unselected rows are not read
+    call("mf_fedavg_reduce_selected", _p(gathered), nclients, stride, out.numel(), _p(selected), max(count_pos, -1),
+         _p(out), _s())
+    _rec(ev)
+
+
 def dp_update_ws_floats(n16: int, n32: int) -> int:
     """Floats of workspace dp_update_scale needs for buffers of these sizes."""
     return int(call("mf_dp_update_ws_floats", int(n16), int(n32)))

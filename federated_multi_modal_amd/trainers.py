@@ -621,13 +621,15 @@ class MaPLeFederated(TrainerX):
         return name, hp
 
     def _robust_cfg(self, get):
-        """FED.ROBUST_AGG and FED.TRIM_K, validated: (None | "median" | "trimmed_mean", trim_k).  ValueError naming the
+        """FED.ROBUST_AGG and FED.TRIM_K, validated: (None | "median" | "trimmed_mean" | "multi_krum", trim_k; Multi-Krum's
+        own keys: _krum_cfg).  ValueError naming the
         key for an unknown name, TRIM_K < 1, a trim that leaves no client, more than 64 clients, another exchange than
         "ordered" or client weights."""
         name = get("ROBUST_AGG", "none")
         name = name.strip().lower() if isinstance(name, str) else name
         if name != "none" and name not in ROBUST:
-            raise ValueError(f"FED.ROBUST_AGG {name!r}: one of {('none',) + ROBUST}")
+            hint = ' (Krum is "multi_krum" with FED.KRUM_M 1)' if name == "krum" else ""
+            raise ValueError(f"FED.ROBUST_AGG {name!r}: one of {('none',) + ROBUST}{hint}")
         trim_k = get("TRIM_K", 1)
         if isinstance(trim_k, bool) or not isinstance(trim_k, int) or trim_k < 1:
             raise ValueError(f"FED.TRIM_K {trim_k!r}: an integer >= 1")
@@ -646,10 +648,42 @@ class MaPLeFederated(TrainerX):
         if not (isinstance(spec, str) and spec.strip().lower() == "uniform"):
             raise ValueError(f'FED.CLIENT_WEIGHTS {spec!r}: FED.ROBUST_AGG needs "uniform" (a weighted median is a '
                              "different statistic)")
-        if self.rank == 0:
+        if self.rank == 0 and name != "multi_krum":  # _krum_cfg reports Multi-Krum, with its own keys
             print("[INFO] Robust aggregation: coordinate-wise " +
                   ("median" if name == "median" else f"trimmed mean, {trim_k} of {self.num_clients} cut at either end"))
         return name, trim_k
+
+    def _krum_cfg(self, get):
+        """FED.KRUM_F and FED.KRUM_M, validated: (f, m).  ValueError naming the key for a value that is not an integer
+        >= 0 and, under FED.ROBUST_AGG multi_krum, for fewer than 2 * KRUM_F + 3 clients (Blanchard et al.'s condition)
+        or a KRUM_M above NUM_CLIENTS - KRUM_F."""
+        f, m = get("KRUM_F", 1), get("KRUM_M", 0)
+        for key, v in (("KRUM_F", f), ("KRUM_M", m)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"FED.{key} {v!r}: an integer >= 0")
+        name = get("ROBUST_AGG", "none")
+        if not (isinstance(name, str) and name.strip().lower() == "multi_krum"):
+            return f, m
+        if self.num_clients < 2 * f + 3:
+            raise ValueError(f"FED.NUM_CLIENTS {self.num_clients}: Multi-Krum with FED.KRUM_F {f} needs at least "
+                             f"2 * KRUM_F + 3 = {2 * f + 3} clients")
+        if m > self.num_clients - f:
+            raise ValueError(f"FED.KRUM_M {m}: at most FED.NUM_CLIENTS - FED.KRUM_F = {self.num_clients - f}")
+        if self.rank == 0:
+            kept = self.num_clients - f if m == 0 else m
+            print(f"[INFO] Robust aggregation: Multi-Krum, f = {f}, the {kept} best-scored of {self.num_clients} "
+                  f"clients kept" + (" (Krum)" if kept == 1 else ""))
+        return f, m
+
+    def _krum_report(self, round_no: int):
+        """Rank 0's line of a round under Multi-Krum: the clients kept and every client's score (one host sync: after
+        the round's wait)."""
+        x = getattr(self, "exchange", None)
+        if x is None or not getattr(x, "krum", False) or self.rank != 0:
+            return
+        kept, scores, p, fe, me = x.krum_stats()
+        print(f"[Round {round_no}] Multi-Krum: kept clients {kept} of {p} present, scores " +
+              ", ".join("absent" if s != s else f"{s:.6g}" for s in scores))
 
     def _dp_cfg(self, get):
         """FED.DP_CLIP, DP_NOISE_MULTIPLIER, DP_DELTA and DP_SEED, validated: {"clip": S or None, "z", "std": the
@@ -806,7 +840,7 @@ class MaPLeFederated(TrainerX):
         """trainers/maple_fed.py:164-176, plus the options the reference lacks (all off by default):
         FED.CLIENT_WEIGHTS (sample-weighted FedAvg, McMahan et al.), FED.PROX_MU (FedProx, Li et al.),
         FED.SERVER_OPT (FedAvgM, Hsu et al.; FedAdagrad / FedAdam / FedYogi, Reddi et al.) and FED.ROBUST_AGG
-        (coordinate-wise median / trimmed mean, Yin et al.), FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
+        (coordinate-wise median / trimmed mean, Yin et al.; Multi-Krum, Blanchard et al.), FED.DP_CLIP / FED.DP_NOISE_MULTIPLIER (DP-FedAvg,
         McMahan et al. 2018), FED.COMPRESS (int8 or top-k uplink compression with error feedback, Alistarh et al.;
         Stich et al.) and FED.DYN_ALPHA (FedDyn, Acar et al.)."""
         global_classnames = list(self.lab2cname.values())
@@ -816,6 +850,7 @@ class MaPLeFederated(TrainerX):
             raise ValueError(f"FED.PROX_MU {mu}: the FedProx coefficient is >= 0 (0 = off)")
         server_opt, server_hp = self._server_opt_cfg(get)
         robust, trim_k = self._robust_cfg(get)
+        krum_f, krum_m = self._krum_cfg(get)
         self.dp = self._dp_cfg(get)
         self.dp_rounds = 0  # rounds that aggregated (n_valid > 0): what the reported epsilon composes over
         self.compress = cp = self._compress_cfg(get)
@@ -844,10 +879,10 @@ class MaPLeFederated(TrainerX):
                                  server=self.server, robust=robust, trim_k=trim_k, dp_clip=self.dp["clip"],
                                  compress=cp["compress"], compress_rounding=cp["rounding"],
                                  error_feedback=cp["error_feedback"], compress_seed=cp["seed"], client=c.client_id,
-                                 dyn=self.dyn, compress_k=cp.get("k", 8))
+                                 dyn=self.dyn, compress_k=cp.get("k", 8), krum_f=krum_f, krum_m=krum_m)
                     for c in self.clients]
         self.exchange = FedAvgExchange(self.fed, mode=mode, robust=robust, trim_k=trim_k, dp_std=self.dp["std"],
-                                       dp_seed=self.dp["seed"])
+                                       dp_seed=self.dp["seed"], krum_f=krum_f, krum_m=krum_m)
         self._compress_report()
         if mu > 0.0:
             # FedProx: every local step reads the bucket's global copy (refreshed in place by each unpack), so the
@@ -984,6 +1019,7 @@ class MaPLeFederated(TrainerX):
         """Wait for the exchange the rank's last client started (FedAvgExchange: every client's bucket then
         holds the sum over all clients), unpack into every local client."""
         self.exchange.finish(late_failed, abort=abort)
+        self._krum_report(getattr(self.exchange, "round", 0))  # finish() has counted the round: 1, 2, ...
         for fed in self.fed:
             fed.unpack()
         return self.fed[0].n_valid()

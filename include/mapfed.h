@@ -397,6 +397,57 @@ int mf_fedavg_reduce_trimmed(const float* gathered, int nclients, int64_t stride
  * mf_fedavg_unpack_weighted and mf_fedopt_step / mf_fedopt_deliver (weighted = 1) consume as they are.          */
 int mf_fedavg_pack_robust(const void* p16, int64_t n16, const float* p32, int64_t n32, const int* invalid_flag,
                           float* bucket, void* stream);
+/* ---- Multi-Krum (Blanchard, El Mhamdi, Guerraoui, Stainer: "Machine Learning with Adversaries: Byzantine Tolerant
+ * Gradient Descent", NeurIPS 2017; keeping the m best: El Mhamdi, Guerraoui, Rouault, ICML 2018): whole clients are
+ * kept or dropped by their squared L2 distances to their nearest peers, over the image mf_fedavg_reduce_trimmed reads
+ * (gathered[c * stride + t], c < nclients <= 64, t < n; an absent client is NaN everywhere).  Every argument check
+ * returns before any launch; plain vector stores, no float atomics.
+ *
+ * The distances, two launches, no host synchronisation, bit-identical run to run:
+ *   D[i][j] = sum_t (double)(x_i[t] - x_j[t])^2 for i <= j, mirrored to D[j][i]: one fp32 subtract, the square and
+ *   the sum in fp64 (the square of an fp32 value is exact in fp64, so a fused multiply-add gives mul + add's bits).
+ *   The diagonal is computed like any pair: +0 for a present client, NaN for an absent one, which is how absence is
+ *   read later.  All n coordinates take part; a difference of +-inf gives +inf.  Never formed from a Gram matrix.
+ *   Order of summation: a workgroup owns a chunk of mf_krum_chunk_elems() coordinates and an 8 x 8 tile of client
+ *   pairs; thread t of 256 adds the groups of 4 coordinates t, t + 256, ... of the chunk in ascending order (one
+ *   16-byte load per client when stride % 4 == 0 and gathered is 16-byte aligned, 4-byte loads otherwise and on the
+ *   ragged tail: the same bits either way), the 64 lanes of a wave are added by an xor butterfly (32, 16, .., 1), the 4
+ *   waves in order, and the second launch adds the chunk partials in chunk order (16 contiguous runs, then the runs in
+ *   order).  So D is a fixed function of (nclients, n, stride) and the values; the number of workgroups does not depend
+ *   on the device.  n = 0 writes the all-zero matrix.
+ * ws: mf_krum_ws_bytes(nclients, n) bytes, 8-byte aligned (-1 for nclients outside 1..64 or n < 0); dist: nclients^2
+ * doubles, row-major.  Errors: nclients outside 1..64, n < 0 or stride < n, a null or misaligned ws / dist, a null
+ * gathered with n > 0.                                                                                            */
+int64_t mf_krum_ws_bytes(int nclients, int64_t n);
+int mf_krum_chunk_elems(void);
+int mf_krum_pairwise(const float* gathered, int nclients, int64_t stride, int64_t n, void* ws, double* dist,
+                     void* stream);
+/* The selection, one workgroup, a deterministic function of (parts, f, m).  parts: [nparts][nclients^2] doubles, the
+ * distance matrices of the coordinate shards:
+ *   - D = parts[0] + parts[1] + ... + parts[nparts - 1] per entry, sequential fp64 adds starting from part 0;
+ *   - client i is present when D[i][i] is not NaN; p = the number of present clients; p = 0 selects nothing;
+ *   - f' = max(min(f, (p - 3) div 2), 0): an f the present clients cannot carry degrades;
+ *   - q = max(p - f' - 2, 0); score_i = the sum of the q smallest D[i][j] over present j != i, the terms taken in
+ *     ascending (value, j) order, sequential fp64 adds starting from the first term (q = 0: +0);
+ *   - m' = p - f' when m = 0 (Multi-Krum), else min(m, p - f') (m = 1: Krum);
+ *   - the m' present clients lowest in (score, index) are selected.
+ * selected[c] = 0 or 1; scores[c] = score_c, the quiet NaN 0x7ff8000000000000 for an absent client; counts =
+ * {p, f', m'}.  Errors: nparts < 1, nclients outside 1..64, f < 0, m < 0, a null pointer.                        */
+int mf_krum_select(const double* parts, int nparts, int nclients, int f, int m, int* selected, double* scores,
+                   int* counts, void* stream);
+/* The mean of the selected clients in mf_fedavg_reduce_trimmed's place.  selected (nclients ints, non-zero =
+ * selected) is read on the device; m' = their number.  Per coordinate t < n:
+ *   - acc = the first selected client's value; acc += the next one's, in client order, one IEEE fp32 add each;
+ *   - out[t] = acc / float(m'), correctly rounded; m' = 0 gives +0;
+ *   - an unselected client is skipped by a select, never multiplied by 0: an absent client's NaNs do not leak;
+ *   - out[count_pos] = float(the number of non-NaN values at that coordinate over all clients) instead (count_pos
+ *     < 0: no such element), as mf_fedavg_reduce_trimmed counts, so the reduced robust bucket reads
+ *     [statistic | 1 | p].
+ * gathered and out must not overlap.  16-byte loads when stride % 4 == 0 and both pointers are 16-byte aligned,
+ * 4-byte loads otherwise and on the ragged tail; the same bits either way.
+ * Errors: nclients < 1 or > 64, n < 0 or stride < n, count_pos >= n, a null pointer with n > 0.                  */
+int mf_fedavg_reduce_selected(const float* gathered, int nclients, int64_t stride, int64_t n, const int* selected,
+                              int64_t count_pos, float* out, void* stream);
 /* ---- DP-FedAvg (McMahan, Ramage, Talwar, Zhang: "Learning Differentially Private Recurrent Language Models",
  * ICLR 2018): per-client update clipping and Gaussian noise on the sum.  Every fp32 operation named below is one
  * IEEE operation rounded on its own (no fused multiply-add), no float atomics, logf / sqrtf / sinf / cosf are the
